@@ -1,7 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- 6-camera lift (LSS view transform + bev_pool_v2) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`).
+Everything else below -- the kernel leg and its `roofline`, the rocprofv3 / PMC
+children, `percall_prepare`, `backward`, `sv`, `veonb`, `veonb_with_2d`,
+`veonl_fp16`, `cpu_baseline` -- runs only with `--full`.  `--dump-outputs DIR`
+writes what the last timed step returned as DIR/<name>.npy (float32 / float64,
+at most 48 MB in all: a larger output is a fixed, seeded sample of its elements;
+the line's `outputs` says which).
 
 A "step" is one pass of the hot path over one synthetic 6-camera sample:
 ``view_transformer.view_transform(input, depth, tran_feat)`` -- the region the
@@ -85,9 +94,17 @@ def parse():
                    help='--shard cameras with VEONB / VEONL: one all-reduce of the un-pooled '
                         'volume, or reduce-scatter over channel slices + sharded max-pool + '
                         'all-gather of the pooled slices (1.78x fewer link bytes)')
+    p.add_argument('--full', action='store_true',
+                   help='also run everything beyond the headline: the kernel leg '
+                        '(roofline, rocprofv3 / PMC children), per-call and backward '
+                        'legs, the sv / veonb / veonl_fp16 sub-objects, the CPU baseline')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write what the last timed step returned as DIR/<name>.npy '
+                        '(float32 / float64, at most 48 MB in all; a larger output is '
+                        'a fixed, seeded sample of its elements)')
     p.add_argument('--placement', action='store_true',
-                   help='also report the kernel into a placement-tuned persistent '
-                        'output volume (veon_amd/placement.py) as roofline.placed')
+                   help='with --full: also report the kernel into a placement-tuned '
+                        'persistent output volume (veon_amd/placement.py) as roofline.placed')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--cpu-seconds', type=float, default=10.0)
     p.add_argument('--no-sv', action='store_true', help='skip the `sv` sub-object')
@@ -184,9 +201,11 @@ def event_ms(fn, iters, warm=5):
     return e0.elapsed_time(e1) / iters
 
 
-def timed_steps(run, steps, warmup, dist, dev, rehearse=False, gpu=True):
+def timed_steps(run, steps, warmup, dist, dev, rehearse=False, gpu=True, keep=None):
     """W warm-up steps, then exactly K steps between barrier + synchronize on both
-    sides; max over ranks."""
+    sides; max over ranks.  `keep` (a list): the last timed step's return value is
+    appended to it (only that one is held, so the allocation pattern of the steps
+    is the same as without)."""
     sync = torch.cuda.synchronize if gpu else (lambda: None)
     for _ in range(warmup):
         run()
@@ -194,8 +213,13 @@ def timed_steps(run, steps, warmup, dist, dev, rehearse=False, gpu=True):
         dist.barrier()
     sync()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        run()
+    if keep is None:
+        for _ in range(steps):
+            run()
+    else:
+        for _ in range(steps - 1):
+            run()
+        keep.append(run())
     sync()
     if dist is not None:
         dist.barrier()
@@ -206,6 +230,54 @@ def timed_steps(run, steps, warmup, dist, dev, rehearse=False, gpu=True):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed
+
+
+DUMP_BUDGET_BYTES = 48 * 10 ** 6   # all the .npy files of one run together
+DUMP_SEED = 0
+
+
+def named_tensors(obj, prefix='out'):
+    """[(name, tensor)] of a step's return value (a tensor, or dicts / lists /
+    tuples of them), in a fixed order."""
+    if isinstance(obj, torch.Tensor):
+        return [(prefix, obj)]
+    items = (sorted(obj.items()) if isinstance(obj, dict) else
+             enumerate(obj) if isinstance(obj, (list, tuple)) else [])
+    out = []
+    for k, v in items:
+        out += named_tensors(v, '%s.%s' % (prefix, k))
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor of `arrays` ([(name, tensor)]) as dirname/<name>.npy,
+    float64 where it is float64 or an integer type, float32 otherwise.  The budget
+    (48 MB) is split evenly; an array larger than its share is replaced by the
+    elements at fixed, seeded flat indices (sorted; the same on every run).
+    -> {name: {'shape', 'dtype', 'elements', 'sampled'}} for the result line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays)) - 4096   # less the .npy header
+    info = {}
+    for name, t in arrays:
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        dt = torch.float64 if wide else torch.float32
+        flat = t.detach().reshape(-1)
+        n, cap = flat.numel(), share // (8 if wide else 4)
+        sampled = n > cap
+        if sampled:
+            g = torch.Generator(device='cpu').manual_seed(DUMP_SEED)
+            idx = torch.randint(0, n, (cap,), generator=g).to(flat.device).sort().values
+            flat = flat[idx]
+        a = flat.to(dt).cpu().numpy()
+        if not sampled:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        info[name] = {'shape': list(t.shape), 'dtype': str(t.dtype).replace('torch.', ''),
+                      'elements': int(a.size),
+                      'sampled': ('%d flat indices, torch.randint seed %d, sorted'
+                                  % (cap, DUMP_SEED)) if sampled else None}
+    return info
 
 
 # ---------------------------------------------------------------------------
@@ -376,11 +448,12 @@ def sv_subobject(dev, pmc, kt):
     return res
 
 
-def veon_path(args, dev, encoder, size, steps, warmup, dist, world):
+def veon_path(args, dev, encoder, size, steps, warmup, dist, world, keep=None):
     """One chained occupancy-path workload -> (ms per step, stage dict, body
     TFLOP/s, launch mode).  The timed step is the whole forward replayed from ONE
     hipGraph (BASELINE configs[4]: "hipGraph-captured forward") unless capture
-    fails or --no-graph is given."""
+    fails or --no-graph is given.  `keep` (a list) receives the forward's outputs
+    of the last timed step."""
     from tools import hotpath_bench
     from veon_amd.graphs import GraphedCallable
     r = hotpath_bench.run_full(encoder, size, dev=str(dev), iters=5, verbose=False)
@@ -389,12 +462,12 @@ def veon_path(args, dev, encoder, size, steps, warmup, dist, world):
         try:
             net, images, geom = r['net'], r['images'], r['geom']
             graphed = GraphedCallable(lambda im: net(im, geom), (images,))
-            step = lambda: graphed.graph.replay()  # noqa: E731  (static input in place)
+            step = graphed.run   # replay on the static input in place
             launch = 'one hipGraph of the whole forward'
         except Exception as e:  # report, do not hide
             print('whole-forward capture failed (%r); eager' % (e,), file=sys.stderr)
     with torch.no_grad():
-        el = timed_steps(step, steps, warmup, dist, dev)
+        el = timed_steps(step, steps, warmup, dist, dev, keep=keep)
     ms = el / steps * 1e3
     body_flops = 8 * 2.0 * 8 * 100 * 100 * 256 * 256 * 27
     tf = body_flops / (r['body_ms'] * 1e-3) / 1e12
@@ -421,6 +494,7 @@ def bench_hotpath(args, rank, world, dev, dist):
     half.set_half_dtype(args.half)   # before any module packs its weights
     enc = 'vitb' if args.workload == 'VEONB' else 'vitl'
     clip = 'ViT-B/16' if enc == 'vitb' else 'ViT-L/14-336'
+    keep = [] if args.dump_outputs else None
     if args.shard == 'cameras':
         from tools import hotpath_bench
         r = hotpath_bench.run_full(enc, (256, 704), dev=str(dev), iters=3, verbose=False)
@@ -444,7 +518,7 @@ def bench_hotpath(args, rank, world, dev, dist):
                 return net.forward_camera_sharded(images, geom, reduce_dtype=rd,
                                                   reduce=args.reduce)
         with torch.no_grad():
-            el = timed_steps(step, args.steps, args.warmup, dist, dev)
+            el = timed_steps(step, args.steps, args.warmup, dist, dev, keep=keep)
         ms = el / args.steps * 1e3
         stages = {k: round(v, 3) for k, v in r.items() if k.endswith('_ms')}
         tf = 8 * 2.0 * 8 * 100 * 100 * 256 * 256 * 27 / (r['body_ms'] * 1e-3) / 1e12
@@ -456,10 +530,13 @@ def bench_hotpath(args, rank, world, dev, dist):
         par = 'cameras of one sample sharded over %d GPUs + RCCL all-reduce' % world
     else:
         ms, stages, tf, launch = veon_path(args, dev, enc, (256, 704), args.steps,
-                                           args.warmup, dist, world)
+                                           args.warmup, dist, world, keep=keep)
         value, scaling, par = world * 1e3 / ms, 'weak', 'replicas x%d' % world
     if rank != 0:
         return
+    outputs = None
+    if keep is not None:
+        outputs = dump_outputs(args.dump_outputs, named_tensors(keep[0]))
     print(json.dumps({
         'metric': '6cam_hotpath_samples_per_sec', 'value': round(value, 2),
         'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -472,7 +549,7 @@ def bench_hotpath(args, rank, world, dev, dist):
         'roofline': {'kernel': 'k_conv3d_k3 (8 launches, AlignNetOcc3D body)', 'bound': 'mfma',
                      'achieved': round(tf, 1), 'peak': MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
                      'frac': round(tf / MFMA_PEAK_TFLOPS, 4), 'traffic': None},
-        'cpu_baseline': None}), flush=True)
+        'cpu_baseline': None, 'outputs': outputs}), flush=True)
 
 
 def main():
@@ -560,7 +637,7 @@ def main():
         p_kept = vt.ranks_bev.numel()
         n_int = vt.interval_starts.numel()
 
-        graph = None
+        graph = graph_out = None
         if not args.no_graph:
             try:
                 s = torch.cuda.Stream()
@@ -571,11 +648,11 @@ def main():
                 torch.cuda.current_stream().wait_stream(s)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph, stream=s):   # the warm-up's stream
-                    step()
+                    graph_out = step()   # each replay rewrites it in place
             except Exception as e:  # report, do not hide
                 print('hipGraph capture failed (%s); running eager' % e,
                       file=sys.stderr)
-                graph = None
+                graph = graph_out = None
         run = graph.replay if graph is not None else step
         launch_probe = None
         if graph is not None:
@@ -602,9 +679,51 @@ def main():
                             'eager_us': round(probe(step), 2),
                             'eager_first_pass_us': round(first, 2)}
             if launch_probe['eager_us'] < launch_probe['hipGraph_us']:
-                run, graph = step, None
+                run, graph, graph_out = step, None, None
 
-        elapsed = timed_steps(run, args.steps, args.warmup, dist, dev, rehearse)
+        keep = [] if args.dump_outputs else None
+        elapsed = timed_steps(run, args.steps, args.warmup, dist, dev, rehearse, keep=keep)
+        ms_per_step = elapsed / args.steps * 1e3
+        value = (world if args.shard == 'replicas' else 1) * args.steps / elapsed
+        result = {
+            'metric': '6cam_lift_samples_per_sec',
+            'value': round(value, 2),
+            'unit': 'samples/s',
+            'n_gpus': world,
+            'steps': args.steps,
+            'warmup': args.warmup,
+            'ms_per_step': round(ms_per_step, 5),
+            'higher_is_better': True,
+            'scaling': 'weak' if args.shard == 'replicas' else 'strong',
+            'vs_baseline': None,
+            'dtype': 'f32',
+            'data': 'synthetic',
+            'config': {
+                'workload': '%s: %d-cam %dx%d, D=%d, C=%d, %dx%dx%d voxels, '
+                            'view_transform(accelerate=True) -> (B,C,Z,Y,X)'
+                            % (args.workload, n_cams, input_size[0], input_size[1],
+                               D, C, X, Y, Z),
+                'points_kept': p_kept, 'intervals': n_int,
+                'launch': 'hipGraph' if graph is not None else 'eager',
+                'launch_probe_us_per_step': launch_probe,
+                'output_volume': 'allocator-placed (torch.empty per step)',
+                'parallelism': ('replicas x%d (one sample per GPU, no collective)' % world
+                                if args.shard == 'replicas' else
+                                'cameras sharded over %d GPUs + all-reduce of the volume'
+                                % world),
+            },
+        }
+        if keep is not None:
+            last = graph_out if graph is not None else keep[0]
+            result['outputs'] = dump_outputs(args.dump_outputs, [('bev_volume', last)]) \
+                if rank == 0 else None
+            del keep, last
+        if not args.full:   # a plain run: the headline only
+            if rank == 0:
+                print(json.dumps(result), flush=True)
+            if dist is not None:
+                dist.destroy_process_group()
+            return
 
         # ---- kernel leg: the fused pool kernel alone, HIP events on the stream it
         # is launched on, into the buffer the allocator hands out (as the step)
@@ -710,8 +829,6 @@ def main():
 
     alg = algorithmic_bytes(n_cams, hf, wf, C, D, p_kept, n_int, Z * Y * X)
     achieved = alg / (kernel_ms * 1e-3) / 1e9
-    ms_per_step = elapsed / args.steps * 1e3
-    value = (world if args.shard == 'replicas' else 1) * args.steps / elapsed
 
     solo = rank == 0 and world == 1
     pmc, pmc_src = ({}, 'not collected')
@@ -734,52 +851,25 @@ def main():
         placement = {'buffers': len(per), 'fast': fast, 'median_us_per_buffer': per,
                      'threshold_us': PLACEMENT_THRESHOLD_US,
                      'mode': 'fast' if fast == len(per) else 'slow' if fast == 0 else 'mixed'}
-    result = {
-        'metric': '6cam_lift_samples_per_sec',
-        'value': round(value, 2),
-        'unit': 'samples/s',
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': round(ms_per_step, 5),
-        'higher_is_better': True,
-        'scaling': 'weak' if args.shard == 'replicas' else 'strong',
-        'vs_baseline': None,
-        'dtype': 'f32',
-        'data': 'synthetic',
-        'config': {
-            'workload': '%s: %d-cam %dx%d, D=%d, C=%d, %dx%dx%d voxels, '
-                        'view_transform(accelerate=True) -> (B,C,Z,Y,X)'
-                        % (args.workload, n_cams, input_size[0], input_size[1],
-                           D, C, X, Y, Z),
-            'points_kept': p_kept, 'intervals': n_int,
-            'launch': 'hipGraph' if graph is not None else 'eager',
-            'launch_probe_us_per_step': launch_probe,
-            'output_volume': 'allocator-placed (torch.empty per step)',
-            'parallelism': ('replicas x%d (one sample per GPU, no collective)' % world
-                            if args.shard == 'replicas' else
-                            'cameras sharded over %d GPUs + all-reduce of the volume' % world),
-        },
-        'roofline': {
-            'kernel': '%s (bev_pool_v2 fused zero-fill+pool+layout)' % kname,
-            'bound': 'hbm',
-            'achieved': round(achieved, 1),
-            'peak': HBM_PEAK_GBS,
-            'unit': 'GB/s',
-            'frac': round(achieved / HBM_PEAK_GBS, 4),
-            'traffic': traffic_of(pmc, kname) if args.workload == 'S2' else None,
-            'traffic_source': pmc_src,
-            'algorithmic_bytes': alg,
-            'kernel_ms': round(kernel_ms, 5),
-            'kernel_ms_source': 'rocprofv3' if rp_ms is not None else 'hip_events',
-            'kernel_ms_rocprof': None if rp_ms is None else round(rp_ms, 5),
-            'rocprof_calls': rp_calls, 'rocprof_source': kt_src,
-            'kernel_ms_hip_events': round(events_ms, 5),
-            'frac_hip_events': round(alg / (events_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            'kernel_launches_timed': kiters,
-            'placement_mode': placement['mode'] if placement else None,
-            'placement': placement,
-        },
+    result['roofline'] = {
+        'kernel': '%s (bev_pool_v2 fused zero-fill+pool+layout)' % kname,
+        'bound': 'hbm',
+        'achieved': round(achieved, 1),
+        'peak': HBM_PEAK_GBS,
+        'unit': 'GB/s',
+        'frac': round(achieved / HBM_PEAK_GBS, 4),
+        'traffic': traffic_of(pmc, kname) if args.workload == 'S2' else None,
+        'traffic_source': pmc_src,
+        'algorithmic_bytes': alg,
+        'kernel_ms': round(kernel_ms, 5),
+        'kernel_ms_source': 'rocprofv3' if rp_ms is not None else 'hip_events',
+        'kernel_ms_rocprof': None if rp_ms is None else round(rp_ms, 5),
+        'rocprof_calls': rp_calls, 'rocprof_source': kt_src,
+        'kernel_ms_hip_events': round(events_ms, 5),
+        'frac_hip_events': round(alg / (events_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+        'kernel_launches_timed': kiters,
+        'placement_mode': placement['mode'] if placement else None,
+        'placement': placement,
     }
     if placed is not None:
         pg = alg / (placed['kernel_ms'] * 1e-3) / 1e9

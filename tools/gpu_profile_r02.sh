@@ -16,11 +16,11 @@ echo "pytest exit $?" | tee -a $OUT/pytest_gpu.log
 tail -n 3 $OUT/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 echo "smoke exit $?"; tail -n 1 $OUT/smoke.log
-timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench exit $?"
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- \
-  python3 $R/bench.py --no-pmc --no-cpu-baseline --no-sv --no-veonb --no-veonl \
+  python3 $R/bench.py --full --no-pmc --no-cpu-baseline --no-sv --no-veonb --no-veonl \
   > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
 echo "bench trace exit $?"
 cd $R

@@ -12,7 +12,7 @@ tail -5 $OUT/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 echo "smoke exit $?" | tee -a $OUT/smoke.log
 tail -2 $OUT/smoke.log
-timeout -k 10 600 python bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench exit $?"
 cat $OUT/bench.json
 tail -3 $OUT/bench.err
