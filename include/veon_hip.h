@@ -663,6 +663,26 @@ int veon_occ_classify(const float *sem, const int64_t *sem_strides, int Q,
                       const float *bin, const int64_t *bin_strides, int B, int zi,
                       int yi, int xi, int Zo, int Yo, int Xo, float *sem_out,
                       float *bin_out, int64_t *cls_out, void *stream);
+/* Open-vocabulary point retrieval, the `retrieval=True` branch of
+ * VEONTemporal.simple_test (detectors/veon_temporal.py:232-241, 331-356;
+ * semantic_net/san_in_veon_temporal.py:195-200, 212, 268-273), without forming the
+ * upsampled feature volume.  feat (B,C,zi,yi,xi): feat_is_half = 1 -> the half type
+ * of the build (e.g. the channels-last interior of a padded volume), 0 -> fp32; both
+ * addressed through five ELEMENT strides {b, c, z, y, x} (>= 0).  bin (B,2,zi,yi,xi)
+ * fp32, any strides.  points: P int32 triples (x, y, z) in the grid (Zo,Yo,Xo), all
+ * of batch element `batch` (datasets/pipelines/loading.py:990-1012).  emb (Q,C) fp32
+ * contiguous prompt embeddings; emb_norms: a workspace of Q floats.  For every point
+ * p and prompt q, with f = trilinear (align_corners=False) upsample of feat at p:
+ *   score[q*P + p] = f.e_q / (max(|f|, 1e-8) * max(|e_q|, 1e-8))
+ *   bin_prob[p]    = softmax(upsampled bin at p)[0]     (bin_prob NULL: skipped)
+ * Points outside the grid get NaN; nothing is read for them.  1 <= C <= 1024, Q >= 1;
+ * channels-last rows must hold C channels (C <= x stride).  No atomics: repeated calls
+ * are bit-identical. */
+int veon_occ_retrieve(const void *feat, int feat_is_half, const int64_t *feat_strides,
+                      int C, const float *bin, const int64_t *bin_strides, int B, int zi,
+                      int yi, int xi, int Zo, int Yo, int Xo, const int *points, int P,
+                      int batch, const float *emb, int Q, float *emb_norms, float *score,
+                      float *bin_prob, void *stream);
 /* ViT token rows -> padded image, with the pixel shuffle of a ConvTranspose2d(k = s,
  * stride = s) folded in (DPTHead.resize_layers[0:2], depth_anything/dpt.py:55-72:
  * the transposed convolution itself is a GEMM over the tokens whose output row holds

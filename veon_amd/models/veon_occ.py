@@ -261,7 +261,7 @@ class VeonOccupancyPath(nn.Module):
         vt = self.view_transformer
         return align_after_lss(volume, adj_metas, vt.grid_config, tuple(vt.ds))
 
-    def _tail(self, x, prev_volumes=None):
+    def _tail(self, x, prev_volumes=None, return_features=False):
         """Conv3d body -> heads -> classifier -> upsampling -> arg-max on a lifted
         PaddedVolume (san_in_veon_temporal.py:196-211, veon_temporal.py:219-227)."""
         dec = self.occ_decoder
@@ -270,17 +270,18 @@ class VeonOccupancyPath(nn.Module):
         x = dec.__dict__['_body'](x, return_volume=True)
         bin_occ = dec.occupancy_pred(x)
         feat = dec.feat_pred(x, return_volume=True)
-        return self._classify(bin_occ, feat)
+        return self._classify(bin_occ, feat, return_features)
 
-    def _classify(self, bin_occ, feat):
+    def _classify(self, bin_occ, feat, return_features=False):
         from .. import conv3d_ops
         W = self.ov_classifier_weight
+        extra = {'feat_low': feat, 'bin_low': bin_occ} if return_features else {}
         if bin_occ.is_cuda and not torch.is_grad_enabled() and bin_occ.shape[1] == 2:
             # upsampling x2, both softmaxes, arg-max and the label volume: one kernel
             low = classifier_logits_low(W, feat)
             sem_occ, bin_up, occ = conv3d_ops.occ_classify(low.float(), bin_occ.float(),
                                                            self.occ_size)
-            return {'bin_occ': bin_up, 'sem_occ': sem_occ, 'occ_pred_cls': occ}
+            return {'bin_occ': bin_up, 'sem_occ': sem_occ, 'occ_pred_cls': occ, **extra}
         sem_occ = semantic_inference_3d_fused(self.ov_classifier_weight, feat, self.occ_size)
         bin_occ = F.interpolate(bin_occ, size=tuple(self.occ_size), mode='trilinear',
                                 align_corners=False)
@@ -289,7 +290,7 @@ class VeonOccupancyPath(nn.Module):
         keep = (score > 0.0) & (torch.softmax(bin_occ, dim=1)[:, 0] > 0.5)
         occ = torch.where(keep, cls, torch.full_like(cls, sem_occ.shape[1]))
         return {'bin_occ': bin_occ, 'sem_occ': sem_occ,
-                'occ_pred_cls': occ.permute(0, 3, 2, 1).contiguous()}
+                'occ_pred_cls': occ.permute(0, 3, 2, 1).contiguous(), **extra}
 
     def lift_cameras(self, images, img_metas, lo, hi, depth=None):
         """The UN-POOLED lifted volume (B, C, Z, Y, X) fp32 of cameras [lo, hi) of
@@ -405,12 +406,12 @@ class VeonOccupancyPath(nn.Module):
             return out
         return vol.view(b, c, z // dz, dz, y // dy, dy, x // dx, dx).amax(dim=(3, 5, 7))
 
-    def from_volume(self, vol):
+    def from_volume(self, vol, return_features=False):
         """Everything after the (reduced) un-pooled lifted volume (B, C, Z, Y, X):
         ds_feat max-pool, Conv3d body, heads, classifier, arg-max."""
-        return self.from_pooled(self._max_pool(vol))
+        return self.from_pooled(self._max_pool(vol), return_features)
 
-    def from_pooled(self, pooled):
+    def from_pooled(self, pooled, return_features=False):
         """Conv3d body, heads, classifier, arg-max on the pooled volume
         (B, C, Z/dz, Y/dy, X/dx)."""
         from .. import conv3d_ops
@@ -418,13 +419,26 @@ class VeonOccupancyPath(nn.Module):
         dec = self.occ_decoder
         if pooled.is_cuda and dec._fast_path(pooled[:, :1, 0]):
             lifted = dec._lift_volume(b, c, pooled.device)
-            return self._tail(conv3d_ops.pack(pooled, out=lifted))
+            return self._tail(conv3d_ops.pack(pooled, out=lifted),
+                              return_features=return_features)
         xx = pooled
         for layer_3d in dec.layers_3d_body:
             xx = layer_3d(xx)
-        return self._classify(dec.occupancy_pred(xx), dec.feat_pred(xx))
+        return self._classify(dec.occupancy_pred(xx), dec.feat_pred(xx), return_features)
 
-    def forward(self, images, img_metas, prev_volumes=None, depth=None, with_2d=False):
+    def retrieve(self, out, points_indices, embeddings, batch=0):
+        """Open-vocabulary point retrieval (the reference's ``retrieval=True`` branch,
+        veon_temporal.py:232-241, 331-356) on the output of ``forward(...,
+        return_features=True)``: ``points_indices`` (P, 3) int32 (x, y, z) voxels of the
+        evaluation grid (``retrieval.points_to_voxel_indices``), ``embeddings`` (Q, C)
+        prompt embeddings -> (score (Q, P), bin_prob (P,)); see
+        ``retrieval.retrieve_points``."""
+        from ..retrieval import retrieve_points
+        return retrieve_points(out['feat_low'], out['bin_low'], points_indices, embeddings,
+                               self.occ_size, batch)
+
+    def forward(self, images, img_metas, prev_volumes=None, depth=None, with_2d=False,
+                return_features=False):
         """images (B, N, 3, H, W); img_metas = (sensor2egos, ego2globals, intrins,
         post_rots, post_trans, bda) as the reference's ``img[1:7]``;
         ``prev_volumes``: aligned lifted volumes of the past frames, newest first
@@ -432,7 +446,10 @@ class VeonOccupancyPath(nn.Module):
         ``occ_size`` and ``occ_pred_cls``.  ``with_2d`` (needs ``side_adapter=True``):
         also the 2-D mask branch the reference always runs beside the 3-D one
         (san_in_veon_temporal.py:123-139), on the SAME CLIP features; its outputs come
-        back under ``2d_*`` keys."""
+        back under ``2d_*`` keys.  ``return_features``: also ``feat_low`` (the sem head's
+        low-resolution feature volume: its PaddedVolume on the native path -- a buffer
+        the module reuses, valid until its next forward -- else (B, C, z, y, x)) and
+        ``bin_low`` (B, 2, z, y, x), the inputs of ``retrieve``."""
         if with_2d and self.side_adapter_network is None:
             raise RuntimeError('VeonOccupancyPath was built without side_adapter=True')
         B, N = images.shape[:2]
@@ -449,11 +466,11 @@ class VeonOccupancyPath(nn.Module):
                                    images.device)
             x = dec.fuse(0, None, feats, [supp], depth2, metas2, None, (hf, wf),
                          out_volume=vol, fused=fused)
-            out = self._tail(x, prev_volumes)
+            out = self._tail(x, prev_volumes, return_features)
             return self._add_2d(out, images, feats) if with_2d else out
         feats, supp, depth = self._branches(images, depth)
         out = dec(sem_embed_ds, feats, [supp], depth, metas, prev_volumes)
-        out = self._classify(out['bin_occ'], out['feat_occ'])
+        out = self._classify(out['bin_occ'], out['feat_occ'], return_features)
         return self._add_2d(out, images, feats) if with_2d else out
 
     def _add_2d(self, out, images, feats):
