@@ -469,10 +469,20 @@ int veon_two_hot_window(int BN, int H, int W, int ds, int D, float lo, float ste
  *                      [B,T,H*64] = softmax(q k^T + bias) v, flash style.
  *                      bias (optional) fp32 [.,.,T,T] with batch / head strides
  *                      in elements (0 = broadcast).  head_dim must be 64.
+ *                      Masking: bias -inf on a key removes it; a query whose keys
+ *                      are ALL masked gets an output row of 0 (torch's softmax
+ *                      gives NaN there).  Any pattern of masked 64-key tiles is
+ *                      exact, however far below zero the live scores lie.
  */
 /* experiment knob of tools/gemm_bench.py: force the tile configuration of
  * veon_vit_gemm (-1 = automatic, 0 = small-tile kernel, 1..6 = ring-kernel tiles) */
 void veon_gemm_ring_set(int config);
+/* Force the small-tile kernel's shape (wm waves down, wn across, mt 16-row blocks per
+ * wave) of veon_vit_gemm when it takes that kernel (veon_gemm_ring_set(0) sends every
+ * shape there); overrides the VEON_GEMM_SMALL=wm,wn,mt knob of tools/gemm_bench.py.
+ * Instantiated: (4,2,1) (4,2,2) (4,4,1) (4,4,2) (8,2,1); any other triple returns
+ * VEON_ERR_BAD_ARG and changes nothing.  wm = -1: back to automatic. */
+int veon_gemm_small_set(int wm, int wn, int mt);
 int veon_vit_cast_bf16(const float *in, void *out_bf16, int64_t n, void *stream);
 /* Patch embedding (dinov2_layers/patch_embed.py: Conv2d(kernel = stride = patch)) as a
  * GEMM operand: img fp32 (B,C,H,W) -> bf16 rows [B*(skip + h*w)][kpad], row element
@@ -610,7 +620,10 @@ int veon_conv3d_k3_bf16(const void *in_padded, const void *w_bf16,
  * runs in bf16.
  */
 /* experiment knob of tools/body_bench.py (ablations of the conv kernels' loads;
- * non-zero flags give WRONG results): 0 = normal. */
+ * non-zero flags give WRONG results): 0 = normal.  Correct-result bits: 8 (bit 3) takes
+ * the general kernel instead of the slab-sharing one; bits 16..27 force the tile (wm, wn,
+ * mt: four bits each) -- while they name a tile that is not instantiated, the conv
+ * entry points return VEON_ERR_BAD_ARG. */
 void veon_conv_debug_set(int flags);
 /* Host-only: the (rows | cols << 16) tile the conv launcher picks for a problem
  * (kd = 3: veon_conv3d_k3_bf16 on B x Z x Y x X voxels; kd = 1: the 2-D convs on

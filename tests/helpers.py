@@ -95,3 +95,53 @@ def named_init_(module, prefix, seed=0, boost=None, skip=()):
                     v = v * factor
             t.copy_(v.to(t.dtype))
     return module
+
+
+# --- the two half flavours of the native library (veon_amd/half.py) -------------------
+import pytest  # noqa: E402
+
+from veon_amd import half  # noqa: E402
+
+# Unit roundoff of a half OUTPUT as the tests state it (half an ulp, relative): bf16 keeps
+# 8 significant bits, fp16 11, so fp16 tolerances are 8x tighter than the bf16 ones.
+ROUNDOFF = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -12}
+
+
+def roundoff(dtype=None):
+    """2^-9 (bf16) or 2^-12 (fp16): of ``dtype``, default the process's half dtype."""
+    return ROUNDOFF[dtype or half.dtype()]
+
+
+def half_tol(rtol, atol, dtype=None):
+    """A tolerance stated for bf16 outputs, scaled to the flavour by unit roundoff:
+    unchanged for bf16, both terms 8x tighter for fp16."""
+    f = roundoff(dtype) / ROUNDOFF[torch.bfloat16]
+    return dict(rtol=rtol * f, atol=atol * f)
+
+
+def to_half(x):
+    """Round to the flavour's half dtype and back (the operands a kernel sees)."""
+    return x.to(half.dtype()).float()
+
+
+@pytest.fixture(autouse=True)
+def flavour(request):
+    """The half flavour a test runs in, as its torch dtype: bf16 for every test of a
+    module that imports this fixture, fp16 for the twins made by ``fp16_twin`` (whose
+    names end in ``_fp16``).  The body runs inside ``half.use(...)``."""
+    fp16 = request.function.__name__.endswith('_fp16')
+    with half.use(torch.float16 if fp16 else torch.bfloat16):
+        yield half.dtype()
+
+
+def fp16_twin(test):
+    """The same test, with the same parametrisation, run in the fp16 flavour under the
+    name ``<test>_fp16``; the original keeps its name and ids and runs in bf16:
+    ``test_x_fp16 = fp16_twin(test_x)``."""
+    import functools
+
+    @functools.wraps(test)
+    def twin(*args, **kwargs):
+        return test(*args, **kwargs)
+    twin.__name__ = twin.__qualname__ = test.__name__ + '_fp16'
+    return twin

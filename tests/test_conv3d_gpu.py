@@ -1,16 +1,19 @@
 """GPU parity of the implicit-GEMM Conv3d body (csrc/conv3d.hip) against plain
-PyTorch fp32 ``conv3d`` / ``BatchNorm3d`` on the same bf16-rounded operands.
+PyTorch fp32 / fp64 ``conv3d`` / ``BatchNorm3d`` on the same half-rounded operands,
+in both half flavours (bf16, fp16) where the kernels take half operands.
 
-Tolerance: operands are bf16 on both sides and accumulation is fp32, so the only
-differences are the fp32 summation order and the final bf16 rounding of the
-kernel's output: |got - want| <= 2^-7 * |want| + 2e-3 * rms(want) per element.
+Tolerance: operands are half on both sides and accumulation is fp32, so the only
+differences are the fp32 summation order and the final half rounding of the
+kernel's output: |got - want| <= 2^-7 * |want| + 2e-3 * rms(want) per element for
+bf16, both terms scaled by unit roundoff for fp16 (tests/helpers.py: half_tol).
 """
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from veon_amd import _lib, conv3d_ops
+from tests.helpers import flavour, fp16_twin, half_tol, to_half  # noqa: F401
+from veon_amd import _lib, conv3d_ops, half
 from veon_amd.models.semantic_net import AlignBody3D, ResBlock3D
 
 pytestmark = pytest.mark.gpu
@@ -18,20 +21,23 @@ DEV = 'cuda:0'
 
 
 def _bf(x):
-    return x.to(torch.bfloat16).float()
+    """Round to the process's half dtype (bf16 unless a test runs under ``flavour``)."""
+    return to_half(x)
 
 
 def _close(got, want):
     rms = want.pow(2).mean().sqrt().item() + 1e-12
     err = (got - want).abs()
-    bound = want.abs() * 2.0 ** -7 + 2e-3 * rms
+    tol = half_tol(2.0 ** -7, 2e-3)     # bf16 as stated above; fp16 8x tighter
+    bound = want.abs() * tol['rtol'] + tol['atol'] * rms
     assert bool((err <= bound).all()), (err.max().item(), rms)
 
 
-def test_pack_unpack_round_trip_and_halo():
+def test_pack_unpack_round_trip_and_halo(flavour):
     g = torch.Generator().manual_seed(0)
     x = _bf(torch.randn(2, 72, 3, 5, 70, generator=g)).to(DEV)
     vol = conv3d_ops.pack(x)
+    assert vol.rows.dtype == flavour
     back = conv3d_ops.unpack(vol)
     assert torch.equal(back, x)
     grid = vol.rows.view(2, 5, 7, 72, 72).float()
@@ -43,10 +49,13 @@ def test_pack_unpack_round_trip_and_halo():
     assert float(vol.storage[vol.guard + vol.M:].abs().sum()) == 0.0
 
 
+test_pack_unpack_round_trip_and_halo_fp16 = fp16_twin(test_pack_unpack_round_trip_and_halo)
+
+
 @pytest.mark.parametrize('B,Cin,Cout,Z,Y,X', [(1, 64, 64, 3, 5, 7), (2, 128, 72, 2, 9, 33),
                                              (1, 64, 136, 1, 1, 1), (1, 192, 256, 4, 20, 21)])
 @pytest.mark.parametrize('mode', ['plain', 'bn_relu', 'bn_resid_relu'])
-def test_conv3d_matches_torch(B, Cin, Cout, Z, Y, X, mode):
+def test_conv3d_matches_torch(B, Cin, Cout, Z, Y, X, mode, flavour):
     g = torch.Generator().manual_seed(Cin + Cout + X)
     x = _bf(torch.randn(B, Cin, Z, Y, X, generator=g)).to(DEV)
     w = _bf(torch.randn(Cout, Cin, 3, 3, 3, generator=g) * (27 * Cin) ** -0.5).to(DEV)
@@ -73,6 +82,9 @@ def test_conv3d_matches_torch(B, Cin, Cout, Z, Y, X, mode):
     assert float(grid.abs().sum()) == 0.0
     assert float(out.storage[:out.guard].abs().sum()) == 0.0
     assert float(out.storage[out.guard + out.M:].abs().sum()) == 0.0
+
+
+test_conv3d_matches_torch_fp16 = fp16_twin(test_conv3d_matches_torch)
 
 
 def test_veon_body_shape_against_torch_on_device():
@@ -226,9 +238,12 @@ def test_hip_body_and_heads_against_reference_vectors():
                                            (1, 64, 32, 20, 41), (6, 128, 64, 36, 50)])
 @pytest.mark.parametrize('mode', ['bias', 'bias_relu', 'bias_resid'])
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
-def test_conv2d_matches_torch(B, Cin, Cout, Y, X, mode, dtype):
+def test_conv2d_matches_torch(B, Cin, Cout, Y, X, mode, dtype, flavour):
     """The 2-D (9-tap) mode of the conv kernel, incl. the 64-wide tiles and the
-    bf16 planar pack / unpack used by the DPT head."""
+    half planar pack / unpack used by the DPT head (``dtype`` bfloat16 stands for the
+    flavour's half type: fp16 in the twin)."""
+    if dtype != torch.float32:
+        dtype = flavour
     if mode == 'bias_resid' and Cin != Cout:
         pytest.skip('identity add needs Cin == Cout')
     g = torch.Generator().manual_seed(Cin * 7 + Cout + X)
@@ -249,7 +264,7 @@ def test_conv2d_matches_torch(B, Cin, Cout, Y, X, mode, dtype):
         want = want + x
         out = conv3d_ops.conv2d_k3(img, wp, None, shift, resid=img)
     got = conv3d_ops.unpack_image(out, dtype, channels=Cout).float()
-    if dtype == torch.bfloat16:
+    if dtype == flavour:
         assert torch.equal(got, conv3d_ops.unpack_image(out, torch.float32, Cout))
     _close(got, want)
     grid = out.rows.view(B, Y + 2, X + 2, -1).float().clone()
@@ -257,8 +272,11 @@ def test_conv2d_matches_torch(B, Cin, Cout, Y, X, mode, dtype):
     assert float(grid.abs().sum()) == 0.0
 
 
+test_conv2d_matches_torch_fp16 = fp16_twin(test_conv2d_matches_torch)
+
+
 @pytest.mark.parametrize('B,C,Y,X', [(1, 64, 5, 7), (6, 256, 36, 50), (2, 128, 9, 33)])
-def test_conv2d_second_residual_and_relu_output(B, C, Y, X):
+def test_conv2d_second_residual_and_relu_output(B, C, Y, X, flavour):
     """veon_conv2d_k3_bf16_ex: out = conv + bias + resid + resid2 and a second image
     holding relu(out) -- FeatureFusionBlock's x0 + RCU1(x1) and the ReLU in front of the
     next ResidualConvUnit (util/blocks.py:49-148) out of one epilogue.  Against torch in
@@ -266,7 +284,7 @@ def test_conv2d_second_residual_and_relu_output(B, C, Y, X):
     pass over `out` would give); the halo of both outputs stays zero; each extra alone."""
     g = torch.Generator().manual_seed(C + X)
     xs = [_bf(torch.randn(B, C, Y, X, generator=g)).to(DEV) for _ in range(3)]
-    x, r1, r2 = (conv3d_ops.pack_image(t.to(torch.bfloat16)) for t in xs)
+    x, r1, r2 = (conv3d_ops.pack_image(t.to(flavour)) for t in xs)
     w = _bf(torch.randn(C, C, 3, 3, generator=g) * (9 * C) ** -0.5).to(DEV)
     bias = torch.randn(C, generator=g).to(DEV)
     wp = conv3d_ops.pack_weight2d(w)
@@ -294,20 +312,29 @@ def test_conv2d_second_residual_and_relu_output(B, C, Y, X):
     _close(conv3d_ops.unpack_image(o3, torch.float32, C), (conv + xs[2].double()).float())
 
 
+test_conv2d_second_residual_and_relu_output_fp16 = fp16_twin(
+    test_conv2d_second_residual_and_relu_output)
+
+
 @pytest.mark.parametrize('size_in,size_out', [((4, 6), (8, 12)), ((9, 25), (18, 50)),
                                               ((144, 400), (252, 700)), ((5, 5), (1, 1))])
-def test_resize_bilinear_matches_interpolate(size_in, size_out):
+def test_resize_bilinear_matches_interpolate(size_in, size_out, flavour):
     g = torch.Generator().manual_seed(size_in[0])
     x = _bf(torch.randn(2, 64, *size_in, generator=g)).to(DEV)
     want = F.interpolate(x, size_out, mode='bilinear', align_corners=True)
     img = conv3d_ops.pack_image(x)
     out = conv3d_ops.resize_bilinear(img, size_out)
     got = conv3d_ops.unpack_image(out)
-    # fp32 blends of the same four bf16 taps, one bf16 rounding at the end
-    assert float((got - _bf(want)).abs().max()) <= 2.0 ** -6 * float(want.abs().max())
+    # fp32 blends of the same four half taps, one half rounding at the end (bf16: 2^-6
+    # of the range; fp16 the same scaled by unit roundoff)
+    bound = half_tol(2.0 ** -6, 0)['rtol'] * float(want.abs().max())
+    assert float((got - _bf(want)).abs().max()) <= bound
     grid = out.rows.view(2, size_out[0] + 2, size_out[1] + 2, 64).float().clone()
     grid[:, 1:-1, 1:-1] = 0
     assert float(grid.abs().sum()) == 0.0
+
+
+test_resize_bilinear_matches_interpolate_fp16 = fp16_twin(test_resize_bilinear_matches_interpolate)
 
 
 def test_fused_semantic_inference_on_padded_volume():
@@ -499,7 +526,7 @@ def test_cat_fusion_lift_mfma_path_feeds_the_lift_without_a_copy():
 
 
 @pytest.mark.parametrize('C,Y,X', [(384, 5, 7), (64, 3, 4), (1024, 2, 3), (520, 4, 4)])
-def test_image_layernorm_matches_torch(C, Y, X):
+def test_image_layernorm_matches_torch(C, Y, X, flavour):
     """LayerNorm over the channels of a padded image: padded bf16 result (zero
     halo) and compact fp32 tokens, against F.layer_norm on the same bf16 rows."""
     g = torch.Generator().manual_seed(C)
@@ -522,7 +549,10 @@ def test_image_layernorm_matches_torch(C, Y, X):
     assert float(halo.abs().sum()) == 0.0
 
 
-def test_layernorm_tokens_to_padded_image_and_convblock_fusions():
+test_image_layernorm_matches_torch_fp16 = fp16_twin(test_image_layernorm_matches_torch)
+
+
+def test_layernorm_tokens_to_padded_image_and_convblock_fusions(flavour):
     """veon_layernorm_f32_to_padded == LayerNorm + staging into the padded bf16
     image; and a dim-384 ConvBlock with pre_ln / residual folded into its first /
     last kernel agrees with the same block given them separately."""
@@ -543,7 +573,7 @@ def test_layernorm_tokens_to_padded_image_and_convblock_fusions():
         halo[:, 1:-1, 1:-1] = 0
         assert float(halo.abs().sum()) == 0.0
         blk = ConvBlock(C, C).to(DEV).eval()
-        blk.conv_dtype = torch.bfloat16
+        blk.conv_dtype = flavour
         before = _lib.CALLS.get('veon_layernorm_f32_to_padded', 0)
         fused = blk(x, (Y, X), residual=x, pre_ln=ln)
         assert _lib.CALLS.get('veon_layernorm_f32_to_padded', 0) == before + 1
@@ -552,9 +582,13 @@ def test_layernorm_tokens_to_padded_image_and_convblock_fusions():
     assert rel < 5e-3, rel
 
 
+test_layernorm_tokens_to_padded_image_and_convblock_fusions_fp16 = fp16_twin(
+    test_layernorm_tokens_to_padded_image_and_convblock_fusions)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('shape', [(2, 64, 64, 9, 13), (1, 128, 192, 18, 50), (2, 64, 8, 5, 4)])
-def test_conv2d_stride2_matches_torch(shape):
+def test_conv2d_stride2_matches_torch(shape, flavour):
     """veon_conv2d_k3s2_bf16 (Conv2d k=3, s=2, p=1; DPTHead.resize_layers[3]) against
     torch's conv2d on the same bf16-rounded operands; odd and even sizes; also equal
     to the stride-1 kernel sampled at every second pixel."""
@@ -563,7 +597,7 @@ def test_conv2d_stride2_matches_torch(shape):
     from veon_amd import conv3d_ops
     B, Cin, Cout, Y, X = shape
     torch.manual_seed(0)
-    x = torch.randn(B, Cin, Y, X, device='cuda:0').bfloat16()
+    x = torch.randn(B, Cin, Y, X, device='cuda:0').to(flavour)
     w = (torch.randn(Cout, Cin, 3, 3, device='cuda:0') * (9 * Cin) ** -0.5)
     bias = torch.randn(Cout, device='cuda:0')
     wp = conv3d_ops.pack_weight2d(w)
@@ -572,20 +606,23 @@ def test_conv2d_stride2_matches_torch(shape):
     img = conv3d_ops.pack_image(x)
     out = conv3d_ops.conv2d_k3s2(img, wp, None, shift)
     got = conv3d_ops.unpack_image(out, torch.float32, Cout)
-    ref = F.conv2d(x.float(), w.bfloat16().float(), bias, stride=2, padding=1)
+    ref = F.conv2d(x.double(), w.to(flavour).double(), bias.double(), stride=2,
+                   padding=1).float()
     assert got.shape == ref.shape
-    err = (got - ref).abs()
-    assert bool((err <= 2 ** -7 * ref.abs() + 2e-3 * ref.pow(2).mean().sqrt()).all()), err.max()
+    _close(got, ref)
     full = conv3d_ops.unpack_image(conv3d_ops.conv2d_k3(img, wp, None, shift), torch.float32,
                                    Cout)
     # (bit-equal only when both kernels sum the taps in the same order: Cin = 64)
-    torch.testing.assert_close(got, full[:, :, ::2, ::2], rtol=2 ** -7, atol=2e-2)
+    torch.testing.assert_close(got, full[:, :, ::2, ::2], **half_tol(2 ** -7, 2e-2))
     if Cin == 64:
         assert torch.equal(got, full[:, :, ::2, ::2])
     # the halo of the result is zero: it can feed the next conv directly
     rows = out.rows.view(B, out.shape[2] + 2, out.shape[3] + 2, -1)
     assert not rows[:, 0].any() and not rows[:, -1].any()
     assert not rows[:, :, 0].any() and not rows[:, :, -1].any()
+
+
+test_conv2d_stride2_matches_torch_fp16 = fp16_twin(test_conv2d_stride2_matches_torch)
 
 
 def test_body_conv_is_deterministic_under_load():
@@ -601,3 +638,124 @@ def test_body_conv_is_deterministic_under_load():
     first = conv3d_ops.conv3d_k3(vol, wp, scale, shift, relu=True).rows.clone()
     for _ in range(30):
         assert torch.equal(conv3d_ops.conv3d_k3(vol, wp, scale, shift, relu=True).rows, first)
+
+
+# Every conv tile the launcher instantiates (VEON_LAUNCH_CONV_T), as (wm, wn, mt): wm x wn
+# waves, mt 16-row blocks per wave, a tile of wm*16*mt rows x 64*wn features.
+CONV_TILES = [(3, 4, 7), (4, 4, 3), (4, 4, 4), (4, 2, 1), (4, 2, 2), (4, 2, 3), (4, 2, 4),
+              (4, 3, 2), (4, 3, 3), (8, 1, 1), (8, 1, 2), (8, 1, 3), (8, 1, 4)]
+GENERAL_KERNEL = 8          # veon_conv_debug_set bit 3: k_conv3d_k3 instead of k_conv3d_k3_ax
+
+
+def _force(tile):
+    wm, wn, mt = tile
+    return (wm << 16) | (wn << 20) | (mt << 24)
+
+
+def _epi_ref(conv, scale, shift, resid, act):
+    """fp64 epilogue: act(conv * scale + shift + resid) over channel dim 1."""
+    shape = (1, -1) + (1,) * (conv.dim() - 2)
+    y = conv
+    if scale is not None:
+        y = y * scale.double().view(shape)
+    y = y + shift.double().view(shape)
+    if resid is not None:
+        y = y + resid.double()
+    return (y, F.relu(y), F.gelu(y))[act].float()
+
+
+@pytest.mark.parametrize('kernel', ['slab', 'general'])
+@pytest.mark.parametrize('tile', CONV_TILES)
+def test_conv_every_tile_against_fp64(tile, kernel, flavour):
+    """Each instantiated tile forced through veon_conv_debug_set (bits 16..27), in the
+    slab-sharing kernel and -- with bit 3 -- the general one: kd = 3, kd = 1 at stride 1
+    and kd = 1 at stride 2 (always the general kernel), activation none / relu / gelu
+    with and without the residual, Cin 64 and 192, Cout 200 (not a multiple of any tile
+    width) on grids whose active rows are not a multiple of any tile height; against
+    F.conv3d / F.conv2d in fp64 on the same half operands.  (Every tile's slab-kernel
+    LDS, 2 * (rows + 8 + cols) * 64 * 2 bytes, is within its 160 KiB limit: none falls
+    back to the general kernel on its own.)"""
+    g = torch.Generator().manual_seed(sum(tile) * 7 + len(kernel))
+    Cout = 200
+
+    def rnd(*shape, s=1.0):
+        return _bf(torch.randn(*shape, generator=g) * s).to(DEV)
+    scale = (torch.rand(Cout, generator=g) + 0.5).to(DEV)
+    shift = torch.randn(Cout, generator=g).to(DEV)
+    flags = _force(tile) | (GENERAL_KERNEL if kernel == 'general' else 0)
+    L = _lib.lib()
+    L.veon_conv_debug_set(flags)
+    try:
+        for i, Cin in enumerate((64, 192)):
+            # kd = 3: 1 x 3 x 5 x 7 voxels, 189 active rows
+            x = rnd(1, Cin, 3, 5, 7)
+            w = rnd(Cout, Cin, 3, 3, 3, s=(27 * Cin) ** -0.5)
+            r = rnd(1, Cout, 3, 5, 7)
+            conv = F.conv3d(x.double(), w.double(), padding=1)
+            for act, with_r in ((0, False), (1, True), (2, bool(i))):
+                out = conv3d_ops.conv3d_k3(conv3d_ops.pack(x), conv3d_ops.pack_weight(w),
+                                           scale, shift,
+                                           resid=conv3d_ops.pack(r) if with_r else None,
+                                           act=('none', 'relu', 'gelu')[act])
+                _close(conv3d_ops.unpack(out),
+                       _epi_ref(conv, scale, shift, r if with_r else None, act))
+            # kd = 1, stride 1: 2 x 9 x 11 pixels, 286 active rows
+            x2 = rnd(2, Cin, 9, 11)
+            w2 = rnd(Cout, Cin, 3, 3, s=(9 * Cin) ** -0.5)
+            r2 = rnd(2, Cout, 9, 11)
+            wp2 = conv3d_ops.pack_weight2d(w2)
+            conv2 = F.conv2d(x2.double(), w2.double(), padding=1)
+            img = conv3d_ops.pack_image(x2)
+            for act, with_r in ((2, False), (0, True), (1, bool(i))):
+                out = conv3d_ops.conv2d_k3(img, wp2, scale, shift,
+                                           resid=conv3d_ops.pack_image(r2) if with_r else None,
+                                           act=('none', 'relu', 'gelu')[act])
+                _close(conv3d_ops.unpack_image(out, torch.float32, Cout),
+                       _epi_ref(conv2, scale, shift, r2 if with_r else None, act))
+            # kd = 1, stride 2 (general kernel whatever bit 3 says): once per tile
+            if kernel == 'general':
+                convs2 = F.conv2d(x2.double(), w2.double(), stride=2, padding=1)
+                for act in (0, 1, 2):
+                    out = conv3d_ops.conv2d_k3s2(img, wp2, scale, shift,
+                                                 act=('none', 'relu', 'gelu')[act])
+                    _close(conv3d_ops.unpack_image(out, torch.float32, Cout),
+                           _epi_ref(convs2, scale, shift, None, act))
+    finally:
+        L.veon_conv_debug_set(0)
+
+
+test_conv_every_tile_against_fp64_fp16 = fp16_twin(test_conv_every_tile_against_fp64)
+
+
+@pytest.mark.parametrize('tile', [(4, 2, 5), (5, 2, 1), (4, 4, 1), (2, 4, 7)])
+def test_conv_forced_tile_not_instantiated_is_refused(tile, flavour):
+    """A forced tile that VEON_LAUNCH_CONV_T does not instantiate: every conv entry
+    point returns VEON_ERR_BAD_ARG while the force is set (no launch of another tile on
+    a grid sized for this one), and works again after veon_conv_debug_set(0)."""
+    x = _bf(torch.randn(1, 64, 2, 3, 4)).to(DEV)
+    w = _bf(torch.randn(64, 64, 3, 3, 3) * 0.05).to(DEV)
+    vol, wp = conv3d_ops.pack(x), conv3d_ops.pack_weight(w)
+    img = conv3d_ops.pack_image(x[:, :, 0])
+    wp2 = conv3d_ops.pack_weight2d(w[:, :, 0])
+    shift = torch.zeros(64, device=DEV)
+    L = _lib.lib()
+    for extra in (0, GENERAL_KERNEL):
+        L.veon_conv_debug_set(_force(tile) | extra)
+        try:
+            calls = (lambda: conv3d_ops.conv3d_k3(vol, wp),
+                     lambda: conv3d_ops.conv2d_k3(img, wp2, None, shift),
+                     lambda: conv3d_ops.conv2d_k3(img, wp2, None, shift,
+                                                  out_relu=conv3d_ops.PaddedImage(
+                                                      1, 64, 3, 4, DEV)),
+                     lambda: conv3d_ops.conv2d_k3s2(img, wp2, None, shift))
+            for call in calls:
+                with pytest.raises(_lib.VeonHipError, match=r'status 1\)'):
+                    call()
+        finally:
+            L.veon_conv_debug_set(0)
+    _close(conv3d_ops.unpack(conv3d_ops.conv3d_k3(vol, wp)),
+           F.conv3d(x.double(), w.double(), padding=1).float())
+
+
+test_conv_forced_tile_not_instantiated_is_refused_fp16 = fp16_twin(
+    test_conv_forced_tile_not_instantiated_is_refused)

@@ -173,3 +173,104 @@ def test_veon_l_preset_fp16_graph_replay():
     for k in ('sem_occ', 'bin_occ'):
         err = (got[k].float() - want[k].float()).abs().max().item()
         assert err <= 5e-3 * max(1.0, want[k].abs().max().item()), (k, err)
+
+
+# --- fp16 range edges at every fp32 -> fp16 conversion site ------------------------------
+# fp16 overflows past 65504 (a finite result of magnitude ~1e5 must come out +-inf, as
+# .to(torch.float16) of the fp64 reference does) and has gradual underflow below 2^-14
+# (results around 1e-6 are subnormals of spacing 2^-24, kept, not flushed to 0).  The
+# values stay clear of 65520 (the overflow tie) and of 0, so fp32 accumulation order
+# cannot flip the outcome; a subnormal may differ from the reference by one ulp.
+SUB_ULP = 2.0 ** -24
+
+
+def _assert_fp16_range(got, ref64):
+    """got: fp16 kernel output; ref64: the fp64 reference of the same values."""
+    want = ref64.to(F16)
+    assert got.dtype == F16
+    big = ref64.abs() > 7e4
+    sub = (ref64.abs() < 2.0 ** -14) & (ref64 != 0)
+    assert big.any() and sub.any()
+    assert torch.isinf(want[big]).all()
+    assert torch.equal(got[big], want[big])                   # +-inf, signs included
+    assert not torch.isinf(got[~big]).any()
+    g, w = got[sub].double(), want[sub].double()
+    assert (g != 0).all(), 'fp16 subnormal results flushed to zero'
+    assert ((g - w).abs() <= SUB_ULP).all(), (g - w).abs().max().item()
+
+
+def _range_values(n, seed):
+    """n values: about a third near +-1e5, a third near +-1e-6, the rest O(1)."""
+    g = torch.Generator().manual_seed(seed)
+    sign = torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0).double()
+    kind = torch.arange(n) % 3
+    mag = torch.where(kind == 0, 1e5 * (1 + torch.rand(n, generator=g).double()),
+                      torch.where(kind == 1, 1e-6 * (1 + 4 * torch.rand(n, generator=g).double()),
+                                  0.5 + torch.rand(n, generator=g).double()))
+    return sign * mag
+
+
+def test_fp16_range_edges_cast():
+    from veon_amd import vit_ops
+    ref = _range_values(4096, 90).float().double()       # the kernel's fp32 input, exactly
+    got = vit_ops.to_bf16(ref.float().to(DEV)).cpu()
+    _assert_fp16_range(got, ref)
+    assert torch.equal(got, ref.float().to(F16))          # round to nearest even, bit for bit
+
+
+def test_fp16_range_edges_gemm_output():
+    """EPI_BF16 out of the small-tile and the ring GEMM: column blocks whose bias is
+    +-1e5 (overflow) and whose operands are ~1e-3 (products ~1e-6: subnormal outputs)."""
+    from veon_amd import _lib, vit_ops
+    M, N, K = 96, 192, 64
+    g = torch.Generator().manual_seed(91)
+    # normal fp16 operands (> 2^-14) whose exact products sum to 0.6e-6 .. 4.5e-6
+    a = (torch.rand(M, K, generator=g) * 2.5e-4 + 1.25e-4).to(F16)
+    w = (torch.rand(N, K, generator=g) * 1.25e-4 + 6.5e-5).to(F16)
+    w[N // 3:2 * N // 3] *= -1
+    bias = torch.zeros(N)
+    bias[:N // 6] = 1e5
+    bias[N // 6:N // 3] = -1.5e5
+    ref = a.double() @ w.double().t() + bias.double()
+    L = _lib.lib()
+    for ring in (0, 1):                        # small-tile kernel, a DMA-ring kernel
+        L.veon_gemm_ring_set(ring)
+        try:
+            got = vit_ops.linear(a.to(DEV), w.to(DEV), bias.to(DEV)).cpu()
+        finally:
+            L.veon_gemm_ring_set(-1)
+        _assert_fp16_range(got, ref)
+
+
+def test_fp16_range_edges_layernorm_output():
+    """LayerNorm's fp16 output: columns with a beta of +-1e5 overflow, columns with a
+    gamma of ~1e-6 and beta 0 land on subnormals."""
+    from veon_amd import vit_ops
+    T, d = 64, 768
+    g = torch.Generator().manual_seed(92)
+    x = torch.randn(T, d, generator=g).double() * 2 + 0.5
+    # the subnormal columns: |x_hat| about 1, clear of 0 (+-3 against a row std of ~2)
+    x[:, 256:512] = torch.where(torch.arange(256) % 2 == 0, 3.0, -3.0).double() \
+        + 0.1 * torch.randn(T, 256, generator=g).double()
+    x = x.float().double()                                   # the kernel's fp32 input
+    gamma = 0.5 + torch.rand(d, generator=g).double()
+    beta = torch.zeros(d).double()
+    beta[:128] = 1e5
+    beta[128:256] = -2e5
+    gamma[256:512] = 1e-6 * (1 + torch.rand(256, generator=g).double())
+    gamma, beta = gamma.float().double(), beta.float().double()
+    ref = torch.nn.functional.layer_norm(x, (d,), gamma, beta, 1e-6)
+    got = vit_ops.layernorm(x.float().to(DEV), gamma.float().to(DEV), beta.float().to(DEV),
+                            eps=1e-6).cpu()
+    _assert_fp16_range(got[:, :512], ref[:, :512])
+
+
+def test_fp16_range_edges_volume_pack():
+    """conv3d_ops.pack: fp32 NCDHW -> the padded fp16 volume, then back to fp32."""
+    from veon_amd import conv3d_ops
+    ref = _range_values(2 * 24 * 3 * 5 * 7, 93).float().double().view(2, 24, 3, 5, 7)
+    vol = conv3d_ops.pack(ref.float().to(DEV))
+    assert vol.rows.dtype == F16
+    got = conv3d_ops.unpack(vol).cpu().to(F16)       # fp16 -> fp32 -> fp16 is exact
+    _assert_fp16_range(got, ref)
+    assert torch.equal(got, ref.float().to(F16))

@@ -367,7 +367,7 @@ def test_no_low_half_op_sel_packed_f32_beside_mfma_in_the_vit_kernels():
     reproducer tools/ubench/pk_opsel_repro.hip); hipcc emits that form on its own from
     scalar code.  The ISA of vit_block.hip (GEMM, attention: where it happened) must not
     contain it in any kernel that has MFMAs.  (tools/check_pk_opsel.py checks every source
-    in both flavours; that takes minutes.)"""
+    in both flavours; that takes minutes.)  Both flavours of vit_block.hip here."""
     import importlib.util
     import shutil
     if shutil.which('hipcc') is None:
@@ -377,3 +377,21 @@ def test_no_low_half_op_sel_packed_f32_beside_mfma_in_the_vit_kernels():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     assert mod.offenders(only={'vit_block.hip'}) == {}
+    assert mod.offenders(flags=('-DVEON_HALF_FP16',), only={'vit_block.hip'}) == {}
+
+
+@pytest.mark.parametrize('flavour', ['bf16', 'fp16'])
+def test_gemm_small_tile_force_accepts_only_instantiated_shapes(flavour):
+    """veon_gemm_small_set: the five small-tile instantiations are accepted, any other
+    triple is VEON_ERR_BAD_ARG (a grid sized for it must never run another kernel);
+    -1 restores the automatic choice.  Host-only state, no launch."""
+    from veon_amd import _lib, half
+    with half.use(flavour):
+        L = _lib.lib()
+        try:
+            for t in ((4, 2, 1), (4, 2, 2), (4, 4, 1), (4, 4, 2), (8, 2, 1)):
+                assert L.veon_gemm_small_set(*t) == 0, t
+            for t in ((4, 2, 3), (8, 2, 2), (2, 2, 1), (4, 3, 1), (0, 0, 0), (8, 1, 1)):
+                assert L.veon_gemm_small_set(*t) == 1, t     # VEON_ERR_BAD_ARG
+        finally:
+            assert L.veon_gemm_small_set(-1, -1, -1) == 0

@@ -4,12 +4,15 @@ tests/test_temporal.py pins to vectors from the reference's own classes.
 
 Tolerances: the gather kernels take bf16 operands on both sides and accumulate in
 fp32; what differs is fp32 evaluation order, the fast exp, and the bf16 rounding
-of the result: |got - want| <= 2^-7 |want| + 4e-3 rms(want).  The whole fusion
-(15+ bf16 layers deep, vs fp32 modules) is held to 3 % of rms.
+of the result: |got - want| <= 2^-7 |want| + 4e-3 rms(want) (bf16; the fp16
+flavour of the deformable attention: both terms scaled by unit roundoff,
+tests/helpers.py: half_tol).  The whole fusion (15+ bf16 layers deep, vs fp32
+modules) is held to 3 % of rms.
 """
 import pytest
 import torch
 
+from tests.helpers import flavour, fp16_twin, half_tol, to_half  # noqa: F401
 from veon_amd import conv3d_ops
 from veon_amd.models.semantic_net import temporal_fusion as tfm
 
@@ -18,20 +21,22 @@ DEV = 'cuda:0'
 
 
 def _bf(x):
-    return x.to(torch.bfloat16).float()
+    """Round to the process's half dtype (bf16 unless a test runs under ``flavour``)."""
+    return to_half(x)
 
 
 def _close(got, want, k=4e-3):
     rms = want.pow(2).mean().sqrt().item() + 1e-12
     err = (got - want).abs()
-    bound = want.abs() * 2.0 ** -7 + k * rms
+    tol = half_tol(2.0 ** -7, k)        # bf16 as stated above; fp16 8x tighter
+    bound = want.abs() * tol['rtol'] + tol['atol'] * rms
     assert bool((err <= bound).all()), (err.max().item(), rms)
 
 
 @pytest.mark.parametrize('B,C,heads,Z,Y,X', [(2, 256, 4, 3, 9, 11), (1, 128, 4, 2, 5, 7),
                                             (1, 256, 4, 1, 1, 1), (1, 64, 2, 8, 13, 10),
                                             (2, 256, 8, 2, 5, 6), (1, 32, 1, 3, 4, 5)])
-def test_deform_attention_matches_torch(B, C, heads, Z, Y, X):
+def test_deform_attention_matches_torch(B, C, heads, Z, Y, X, flavour):
     g = torch.Generator().manual_seed(C + X)
     kv = _bf(torch.randn(B, 2 * C, Z, Y, X, generator=g)).to(DEV)
     q = _bf(torch.randn(B, C, Z, Y, X, generator=g)).to(DEV)
@@ -46,6 +51,9 @@ def test_deform_attention_matches_torch(B, C, heads, Z, Y, X):
     halo = got.rows.view(B, Z + 2, Y + 2, X + 2, C).clone()
     halo[:, 1:-1, 1:-1, 1:-1] = 0
     assert float(halo.abs().sum()) == 0.0
+
+
+test_deform_attention_matches_torch_fp16 = fp16_twin(test_deform_attention_matches_torch)
 
 
 def test_deform_attention_rejects_bad_shapes():

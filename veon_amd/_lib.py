@@ -79,6 +79,7 @@ _SIGNATURES = {
     'veon_two_hot_window_slots': (_ci, [_ci, _cf, _cf]),
     'veon_two_hot_window': (_ci, [_ci] * 5 + [_cf] * 4 + [_ci, _vp, _vp, _vp, _vp]),
     'veon_gemm_ring_set': (None, [_ci]),
+    'veon_gemm_small_set': (_ci, [_ci, _ci, _ci]),
     'veon_vit_cast_bf16': (_ci, [_vp, _vp, _i64, _vp]),
     'veon_vit_layernorm': (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _cf, _vp]),
     'veon_vit_layernorm_padded': (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _vp]),

@@ -888,6 +888,18 @@ static ConvTile conv_pick_tile(int kd, int B, int Z, int Y, int X, int Cin, int 
   return ConvTile{wm, wn, mt};
 }
 
+// The tiles VEON_LAUNCH_CONV_T instantiates.  A tile forced through bits 16..27 of
+// veon_conv_debug_set that is not one of them is refused (VEON_ERR_BAD_ARG), never
+// launched as another tile on a grid sized for it.
+static bool conv_tile_instantiated(ConvTile t) {
+  static const ConvTile inst[] = {{3, 4, 7}, {4, 4, 3}, {4, 4, 4}, {4, 2, 1}, {4, 2, 2},
+                                  {4, 2, 3}, {4, 2, 4}, {4, 3, 2}, {4, 3, 3}, {8, 1, 1},
+                                  {8, 1, 2}, {8, 1, 3}, {8, 1, 4}};
+  for (const ConvTile& c : inst)
+    if (c.wm == t.wm && c.wn == t.wn && c.mt == t.mt) return true;
+  return false;
+}
+
 static int conv_k3_impl(int kd, const void* in_padded, const void* w_bf16,
                         const float* scale, const float* shift,
                         const void* resid_padded, void* out_padded, int B, int Z,
@@ -912,6 +924,7 @@ static int conv_k3_impl(int kd, const void* in_padded, const void* w_bf16,
   const int64_t M = (int64_t)B * (Z + 2 * pz) * (Y + 2) * (X + 2);
   if (M > 0x3fffffffLL) return VEON_ERR_BAD_ARG;
   const ConvTile tile = conv_pick_tile(kd, B, Z, Y, X, Cin, Cout, stride);
+  if (!conv_tile_instantiated(tile)) return VEON_ERR_BAD_ARG;
   const int wm = tile.wm, wn = tile.wn, mt = tile.mt;
   const int bm = wm * 16 * mt;
   const int64_t ncol = (Cout + 64 * wn - 1) / (64 * wn);
@@ -966,7 +979,7 @@ static int conv_k3_impl(int kd, const void* in_padded, const void* w_bf16,
     else if (VEON_TILE_IS(8, 1, 4)) VEON_LAUNCH_CONV(8, 1, 4, ACT, RESID);    \
     else if (VEON_TILE_IS(4, 2, 3)) VEON_LAUNCH_CONV(4, 2, 3, ACT, RESID);    \
     else if (VEON_TILE_IS(4, 2, 4)) VEON_LAUNCH_CONV(4, 2, 4, ACT, RESID);    \
-    else VEON_LAUNCH_CONV(4, 2, 1, ACT, RESID);                               \
+    else VEON_LAUNCH_CONV(4, 2, 1, ACT, RESID); /* (checked above) */         \
   } while (0)
   if (relu == 1) {
     if (R) VEON_LAUNCH_CONV_T(1, true); else VEON_LAUNCH_CONV_T(1, false);

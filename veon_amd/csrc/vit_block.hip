@@ -18,6 +18,7 @@
 // V^T) as the MFMA "A" operand and the ACTIVATION (or Q, or P) as "B": the
 // accumulator then holds 4 consecutive output features of ONE token per lane
 // (16-byte epilogue accesses, per-token softmax statistics stay lane-local).
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -954,7 +955,7 @@ __global__ __launch_bounds__(256, 3) void k_attention(
   }
 
   const int nt = (T + AK - 1) / AK;
-  auto tile = [&](int t, auto tail_tag, float floor_) {
+  auto tile = [&](int t, auto tail_tag) {
     constexpr bool TAIL = decltype(tail_tag)::value;
     const int k0 = t * AK;
     const bf16_t* sK = smem + (t & 1) * 2 * KV_ELEMS;
@@ -1019,7 +1020,12 @@ __global__ __launch_bounds__(256, 3) void k_attention(
       mx[i] = m;
     }
     // The reference maximum of a query moves only when a score of this tile stands
-    // more than kAttRise above it (or at tile 0, which sets it).  The decision is per
+    // more than kAttRise above it, or while it is not set yet: until a tile has had a
+    // finite maximum for the query, its row sum is exactly 0 (after a move the maximum
+    // key contributes exp2(0) = 1, and the sum never falls below that), so "l == 0"
+    // is that state, per query and without a flag.  Tile 0 is not special: when it is
+    // fully masked (bias -inf), the first tile with a live key sets the reference, so
+    // live scores far below zero do not underflow to a row of 0.  The decision is per
     // query (the row maximum is formed over the four lane rows first, so the lanes
     // of a query agree), and when any query of the wave moves, everything that still
     // stands at the old reference -- O, the row sums, the reference and this tile's
@@ -1030,14 +1036,15 @@ __global__ __launch_bounds__(256, 3) void k_attention(
 #pragma unroll
     for (int i = 0; i < QT; ++i) {
       const float m = max_over_rows(mx[i]);
-      d[i] = (m > kAttRise || m < floor_) ? m : 0.f;
+      d[i] = (m > kAttRise || ol[i][0] == 0.f) ? m : 0.f;
       if (d[i] == -INFINITY) d[i] = 0.f;  // a fully masked row (bias of -inf)
       any_move |= d[i] != 0.f;
     }
     if (__any(any_move)) {
 #pragma unroll
       for (int i = 0; i < QT; ++i) {
-        // (tile 0 may move DOWN by any amount: O and the sums are 0 there, keep corr finite)
+        // (the first move may go DOWN by any amount: O and the sums are 0 there, keep
+        // corr finite)
         const float corr = __builtin_amdgcn_exp2f(fminf(-d[i], 100.f));
         // Both factors as REAL register pairs (x, x), and the updates written on
         // pairs: left to itself hipcc packs the scalar form into v_pk_add_f32 /
@@ -1101,19 +1108,15 @@ __global__ __launch_bounds__(256, 3) void k_attention(
   };
 
   __syncthreads();  // tile 0 landed
-  float floor_ = INFINITY;
   for (int t = 0; t < nt; ++t) {
     if (t + 1 < nt) dma((t + 1) & 1, (t + 1) * AK);  // flies under this tile
     if (q0 < T) {  // waves past the last query only feed the DMA and barriers
+      // (no state of the loop depends on t == 0, so nothing invites the compiler to
+      // peel tile 0 out of it, which would cost 80 registers of copied accumulators)
       if ((t + 1) * AK > T)
-        tile(t, std::true_type{}, floor_);
+        tile(t, std::true_type{});
       else
-        tile(t, std::false_type{}, floor_);
-      // Tile 0 sets the reference (any maximum counts as "below the floor" of +inf);
-      // from then on it only rises.  The empty asm keeps the compiler from peeling
-      // tile 0 out of the loop, which costs 80 registers of copied accumulators.
-      floor_ = -INFINITY;
-      asm volatile("" : "+s"(floor_));
+        tile(t, std::false_type{});
     }
     __syncthreads();  // next tile landed, this one fully consumed
   }
@@ -1474,6 +1477,44 @@ int veon_vit_gemm_splitk(const void* a_bf16, const void* w_bf16, const float* bi
   return launch_status();
 }
 
+// The small-tile kernel's instantiations (VEON_LAUNCH_GEMM_MT below), as wm*100 +
+// wn*10 + mt; a force of any other triple is refused, never launched as (4,2,1).
+static bool gemm_small_instantiated(int wm, int wn, int mt) {
+  static const int inst[] = {421, 422, 441, 442, 821};
+  for (int c : inst)
+    if (wm * 100 + wn * 10 + mt == c) return true;
+  return false;
+}
+
+// forced small-tile shape (wm*100 + wn*10 + mt; 0 = automatic): veon_gemm_small_set,
+// else the VEON_GEMM_SMALL=wm,wn,mt knob of tools/gemm_bench.py, read once
+static int g_gemm_small = -1;   // -1: not set by the setter, take the environment
+static int gemm_small_forced() {
+  if (g_gemm_small >= 0) return g_gemm_small;
+  static const int env = [] {
+    const char* e = getenv("VEON_GEMM_SMALL");
+    int a = 0, b = 0, c = 0;
+    if (!e || sscanf(e, "%d,%d,%d", &a, &b, &c) != 3) return 0;
+    if (!gemm_small_instantiated(a, b, c)) {
+      fprintf(stderr, "veon: VEON_GEMM_SMALL=%s is not an instantiated small-tile shape "
+                      "(4,2,1 4,2,2 4,4,1 4,4,2 8,2,1); ignored\n", e);
+      return 0;
+    }
+    return a * 100 + b * 10 + c;
+  }();
+  return env;
+}
+
+int veon_gemm_small_set(int wm, int wn, int mt) {
+  if (wm < 0) {
+    g_gemm_small = -1;
+    return VEON_OK;
+  }
+  if (!gemm_small_instantiated(wm, wn, mt)) return VEON_ERR_BAD_ARG;
+  g_gemm_small = wm * 100 + wn * 10 + mt;
+  return VEON_OK;
+}
+
 void veon_gemm_ring_set(int config) {
   g_gemm_ring = config & 0xff;
   if (config < 0) g_gemm_ring = -1;
@@ -1595,13 +1636,9 @@ int veon_vit_gemm(const void* a_bf16, const void* w_bf16, const float* bias,
   int wm = 4, wn = 2;
   int mt = ((int64_t)((M + 63) / 64) * ((N + 127) / 128) > 8 * kNumCU) ? 2 : 1;
   {
-    // experiment knob (tools/gemm_bench.py): VEON_GEMM_SMALL=wm,wn,mt forces the small-tile
-    // kernel's shape among the instantiated ones
-    static const int forced = [] {
-      const char* e = getenv("VEON_GEMM_SMALL");
-      int a = 0, b = 0, c = 0;
-      return (e && sscanf(e, "%d,%d,%d", &a, &b, &c) == 3) ? a * 100 + b * 10 + c : 0;
-    }();
+    // veon_gemm_small_set / VEON_GEMM_SMALL=wm,wn,mt (tools/gemm_bench.py) force the
+    // small-tile kernel's shape among the instantiated ones (checked there)
+    const int forced = gemm_small_forced();
     if (forced) { wm = forced / 100; wn = (forced / 10) % 10; mt = forced % 10; }
   }
   const int bm = wm * 16 * mt, bn = 64 * wn;
@@ -1624,7 +1661,8 @@ int veon_vit_gemm(const void* a_bf16, const void* w_bf16, const float* bias,
     else if (VEON_T(4, 4, 1)) VEON_LAUNCH_GEMM(EPI, 4, 4, 1);                  \
     else if (VEON_T(4, 4, 2)) VEON_LAUNCH_GEMM(EPI, 4, 4, 2);                  \
     else if (VEON_T(8, 2, 1)) VEON_LAUNCH_GEMM(EPI, 8, 2, 1);                  \
-    else VEON_LAUNCH_GEMM(EPI, 4, 2, 1);                                       \
+    else if (VEON_T(4, 2, 1)) VEON_LAUNCH_GEMM(EPI, 4, 2, 1);                  \
+    else return VEON_ERR_BAD_ARG;  /* grid sized for another tile */           \
   } while (0)
   switch (epilogue) {
     case EPI_BF16: VEON_LAUNCH_GEMM_MT(EPI_BF16); break;
