@@ -15,6 +15,16 @@
  *     C = 256: bev_pool_cuda.cu:41,46).
  * Paths below are relative to the reference tree.
  */
+/*
+ * The ctypes binding (veon_amd/_lib.py) reads its argument types from THIS file, so
+ * every declaration below keeps to one style: C89 prototypes `ret veon_name(args);`
+ * (they may span lines) with ret in {int, int64_t, void, const char *} and parameters
+ * int / int64_t / float / unsigned or a pointer (any pointer is passed as an address);
+ * `(void)` for no parameters; comments are C block comments; the only other statement
+ * is the one `typedef struct`.  Anything else makes the binding raise at import.
+ * Prototypes are grouped by the source file under veon_amd/csrc/ that defines them;
+ * every entry point that launches work ends in `void *stream`.
+ */
 #ifndef VEON_HIP_H_
 #define VEON_HIP_H_
 
@@ -42,6 +52,8 @@ extern "C" {
 #define VEON_FEAT_F32 0
 #define VEON_FEAT_F16 1  /* IEEE half */
 #define VEON_FEAT_BF16 2
+
+/* ======== bev_pool_v2.hip =========================================================== */
 
 int veon_abi_version(void);
 /* 16-bit operand type this build of the library was compiled for: 0 = bf16
@@ -148,6 +160,84 @@ int veon_bev_pool_v2_fwd_maxpool(int c, int n_intervals, int batch, int Z, int Y
                                  void *stream);
 
 /*
+ * Half-precision feature rows.  QuickCumsumCuda.forward widens feat to fp32
+ * before the kernel (bev_pool.py:21 `feat.contiguous().float()`); the *_ex
+ * entry points read fp16 / bf16 rows (`feat_dtype` = VEON_FEAT_*) and widen in
+ * registers -- identical arithmetic (the widening is exact, the fmaf chain and
+ * the output stay fp32) at half the gather bytes and no fp32 copy of feat.
+ * With VEON_FEAT_F32 they are the functions above.
+ */
+int veon_bev_pool_v2_fwd_fused_ex(int c, int n_intervals, int batch,
+                                  int64_t voxels_per_batch, const float *depth,
+                                  const void *feat, int feat_dtype,
+                                  const int *ranks_depth, const int *ranks_feat,
+                                  const int *ranks_bev,
+                                  const int *interval_starts,
+                                  const int *interval_lengths, const int *plan,
+                                  float *out, int out_layout, void *stream);
+int veon_bev_pool_v2_fwd_maxpool_ex(int c, int n_intervals, int batch, int Z,
+                                    int Y, int X, int dz, int dy, int dx,
+                                    const float *depth, const void *feat,
+                                    int feat_dtype, const int *ranks_depth,
+                                    const int *ranks_feat, const int *ranks_bev,
+                                    const int *interval_starts,
+                                    const int *interval_lengths,
+                                    const int *row_first, float *out,
+                                    void *stream);
+
+/* As veon_bev_pool_v2_fwd_fused_ex with the (B,C,Z,Y,X) layout, but the channel
+ * planes of `out` are `plane_stride` floats apart (>= voxels_per_batch): out is a
+ * (B, C, plane_stride) buffer whose first voxels_per_batch floats of every plane
+ * are written.  For consumers that take a strided view, and for
+ * tools/stride_probe.py (placement sensitivity of the plane streams). */
+int veon_bev_pool_v2_fwd_fused_strided(int c, int n_intervals, int batch,
+                                       int64_t voxels_per_batch, const float *depth,
+                                       const void *feat, int feat_dtype,
+                                       const int *ranks_depth, const int *ranks_feat,
+                                       const int *ranks_bev,
+                                       const int *interval_starts,
+                                       const int *interval_lengths, const int *plan,
+                                       float *out, int64_t plane_stride,
+                                       void *stream);
+
+/* (images, C, HW) -> (images, HW, C), 4- or 2-byte elements: the
+ * `feat.permute(0, 1, 3, 4, 2)` of view_transform_core (view_transformer.py:273-275)
+ * made contiguous, as bev_pool_v2 does on entry (bev_pool.py:21). */
+int veon_feat_nchw_to_nhwc(const void *in, void *out, int elem_bytes, int images,
+                           int C, int HW, void *stream);
+
+/*
+ * The fused pool + max-pool writing straight into the Conv3d body's input: the
+ * interior of the zero-padded channels-last bf16 grid [B][Z/dz+2][Y/dy+2][X/dx+2][C]
+ * (see veon_conv3d_k3_bf16; allocate it zeroed once, the halo is never
+ * written).  Values are the fp32 results of veon_bev_pool_v2_fwd_maxpool_ex
+ * rounded to bf16 -- what veon_volume_pack_bf16 of that tensor would store.
+ */
+int veon_bev_pool_v2_fwd_maxpool_padded(int c, int n_intervals, int batch, int Z,
+                                        int Y, int X, int dz, int dy, int dx,
+                                        const float *depth, const void *feat,
+                                        int feat_dtype, const int *ranks_depth,
+                                        const int *ranks_feat,
+                                        const int *ranks_bev,
+                                        const int *interval_starts,
+                                        const int *interval_lengths,
+                                        const int *row_first,
+                                        void *out_padded_bf16, void *stream);
+
+/*
+ * 2x2x2 block max of a (B,C,Z,Y,X) fp32 volume -> (B,C,Z/2,Y/2,X/2) fp32: the
+ * ds_feat step of LSSViewTransformerRaw.forward (view_transformer_raw.py:549-553:
+ * rearrange + max over the three block axes) as one streaming pass, for volumes that
+ * did not come out of the fused pool + max-pool kernel (the camera-sharded path: the
+ * block max follows the cross-rank sum).  planes = B * C; Z, Y, X even.  NaN
+ * propagates as in torch.amax.
+ */
+int veon_volume_maxpool2_f32(const float *in, float *out, int64_t planes, int Z, int Y,
+                             int X, void *stream);
+
+/* ======== bev_pool_rows.hip ========================================================= */
+
+/*
  * ---- "row" kernels: the wide-channel shapes (VEON: C = 256) ----------------
  * Same arithmetic as the fused entry points above (serial fmaf chain per voxel
  * in storage order, bev_pool_cuda.cu:38-43), different decomposition: the index
@@ -173,25 +263,6 @@ int veon_bev_pool_v2_fwd_maxpool(int c, int n_intervals, int batch, int Z, int Y
  * feat_elems: number of elements of `feat` (rows * c); must be < 2^31 (row offsets
  *   are 32-bit inside the kernels; every ranks_feat value must be a valid row).
  */
-/*
- * 2x2x2 block max of a (B,C,Z,Y,X) fp32 volume -> (B,C,Z/2,Y/2,X/2) fp32: the
- * ds_feat step of LSSViewTransformerRaw.forward (view_transformer_raw.py:549-553:
- * rearrange + max over the three block axes) as one streaming pass, for volumes that
- * did not come out of the fused pool + max-pool kernel (the camera-sharded path: the
- * block max follows the cross-rank sum).  planes = B * C; Z, Y, X even.  NaN
- * propagates as in torch.amax.
- */
-int veon_volume_maxpool2_f32(const float *in, float *out, int64_t planes, int Z, int Y,
-                             int X, void *stream);
-
-/* experiment knob of tools/poolbench.py / tools/xcd_order_ab.py; 0 = production.
- * bits 0-3: ablations of the row max-pool kernel (results invalid); bit 4: tile =
- * blockIdx instead of the XCD-grouped tile order; bits 8-11: (lg + 1) forces runs of
- * 2^lg tiles per XCD -- the order never changes a result. */
-void veon_pool_debug_set(int flags);
-/* tuning knobs of the row max-pool kernel (0 = built-in default): worker
- * workgroups, longest cold list, longest warm list */
-void veon_pool_tune_set(int workers, int cold_max, int warm_max);
 int64_t veon_bev_pool_voxel_table_ints(int batch, int64_t voxels_per_batch);
 int veon_bev_pool_voxel_table(int n_intervals, int n_points, int batch,
                               int64_t voxels_per_batch, const int *ranks_bev,
@@ -208,6 +279,7 @@ int veon_bev_pool_v2_fwd_rows_maxpool(int c, int batch, int Z, int Y, int X, int
                                       const int *ranks_depth, const int *ranks_feat,
                                       const int *vstart, void *out, int out_padded_bf16,
                                       int64_t feat_elems, void *stream);
+
 /*
  * The same with a caller-given order of the short-list ("cold") work: the pooled
  * volume is cut into chunks of veon_bev_pool_rows_maxpool_chunk() consecutive pooled
@@ -226,50 +298,7 @@ int veon_bev_pool_v2_fwd_rows_maxpool_ordered(
     const int *vstart, void *out, int out_padded_bf16, int64_t feat_elems,
     const int *chunk_order, void *stream);
 
-/*
- * Half-precision feature rows.  QuickCumsumCuda.forward widens feat to fp32
- * before the kernel (bev_pool.py:21 `feat.contiguous().float()`); the *_ex
- * entry points read fp16 / bf16 rows (`feat_dtype` = VEON_FEAT_*) and widen in
- * registers -- identical arithmetic (the widening is exact, the fmaf chain and
- * the output stay fp32) at half the gather bytes and no fp32 copy of feat.
- * With VEON_FEAT_F32 they are the functions above.
- */
-int veon_bev_pool_v2_fwd_fused_ex(int c, int n_intervals, int batch,
-                                  int64_t voxels_per_batch, const float *depth,
-                                  const void *feat, int feat_dtype,
-                                  const int *ranks_depth, const int *ranks_feat,
-                                  const int *ranks_bev,
-                                  const int *interval_starts,
-                                  const int *interval_lengths, const int *plan,
-                                  float *out, int out_layout, void *stream);
-/* (images, C, HW) -> (images, HW, C), 4- or 2-byte elements: the
- * `feat.permute(0, 1, 3, 4, 2)` of view_transform_core (view_transformer.py:273-275)
- * made contiguous, as bev_pool_v2 does on entry (bev_pool.py:21). */
-int veon_feat_nchw_to_nhwc(const void *in, void *out, int elem_bytes, int images,
-                           int C, int HW, void *stream);
-/* As veon_bev_pool_v2_fwd_fused_ex with the (B,C,Z,Y,X) layout, but the channel
- * planes of `out` are `plane_stride` floats apart (>= voxels_per_batch): out is a
- * (B, C, plane_stride) buffer whose first voxels_per_batch floats of every plane
- * are written.  For consumers that take a strided view, and for
- * tools/stride_probe.py (placement sensitivity of the plane streams). */
-int veon_bev_pool_v2_fwd_fused_strided(int c, int n_intervals, int batch,
-                                       int64_t voxels_per_batch, const float *depth,
-                                       const void *feat, int feat_dtype,
-                                       const int *ranks_depth, const int *ranks_feat,
-                                       const int *ranks_bev,
-                                       const int *interval_starts,
-                                       const int *interval_lengths, const int *plan,
-                                       float *out, int64_t plane_stride,
-                                       void *stream);
-int veon_bev_pool_v2_fwd_maxpool_ex(int c, int n_intervals, int batch, int Z,
-                                    int Y, int X, int dz, int dy, int dx,
-                                    const float *depth, const void *feat,
-                                    int feat_dtype, const int *ranks_depth,
-                                    const int *ranks_feat, const int *ranks_bev,
-                                    const int *interval_starts,
-                                    const int *interval_lengths,
-                                    const int *row_first, float *out,
-                                    void *stream);
+/* ======== lss_prepare.hip =========================================================== */
 
 /*
  * The per-camera 3x3 algebra of get_lidar_coor
@@ -316,6 +345,17 @@ int veon_lidar_coor(int B, int N, int D, int H, int W, const float *xs,
  */
 int64_t veon_lss_prepare_workspace_bytes(int64_t num_points,
                                          int64_t num_voxels_total);
+int veon_lss_prepare(int B, int N, int D, int H, int W, const float *coor,
+                     const float *xs, const float *ys, const float *ds,
+                     const float *post_rots_inv, const float *post_trans,
+                     const float *combine, const float *trans, const float *bda,
+                     const float *grid_lower, const float *grid_interval,
+                     const float *grid_size, int64_t voxels_per_batch,
+                     void *workspace, int64_t workspace_bytes, int *ranks_bev,
+                     int *ranks_depth, int *ranks_feat, int *interval_starts,
+                     int *interval_lengths, int *plan, int *counts,
+                     void *stream);
+
 /*
  * The same prepare straight from the reference's per-camera tensors
  * (get_lidar_coor's arguments, view_transformer_raw.py:121-158: sensor2ego
@@ -331,14 +371,6 @@ int64_t veon_lss_prepare_workspace_bytes(int64_t num_points,
  *     call leaves the histogram zeroed again, so no memset node is needed.
  *     With 0 the histogram is cleared first (hipMemsetAsync).
  */
-/*
- * AlignNetOcc3D.prepare_meta (align_net_occ3d.py:328-352) for one frame: out[b,n] =
- * inverse(ego2global[b,0]) @ ego2global[b,n] @ sensor2ego[b,n], (B,N,4,4) fp32 in and
- * out, the algebra in double precision (the reference casts to double, too).
- */
-int veon_sensor2keyego(int B, int N, const float *sensor2ego, const float *ego2global,
-                       float *out, void *stream);
-
 int veon_lss_prepare_cameras(int B, int N, int D, int H, int W, const float *xs,
                              const float *ys, const float *ds,
                              const float *sensor2ego, const float *cam2imgs,
@@ -350,6 +382,7 @@ int veon_lss_prepare_cameras(int B, int N, int D, int H, int W, const float *xs,
                              int *ranks_bev, int *ranks_depth, int *ranks_feat,
                              int *interval_starts, int *interval_lengths, int *plan,
                              int *vstart, int *counts, void *stream);
+
 /*
  * Sparse lift (opt-in): the same prepare, but a frustum point whose
  * depth weight depth_weights[(b,n,d,h,w)] (the (B,N,D,H,W) tensor the pool will
@@ -370,6 +403,7 @@ int veon_lss_prepare_cameras_sparse(
     int *ranks_depth, int *ranks_feat, int *interval_starts, int *interval_lengths,
     int *plan, int *vstart, int *counts, const float *depth_weights, float depth_eps,
     void *stream);
+
 /*
  * Two-hot lift by construction (view_transformer_raw.py:406-429 +
  * 244-302 in one): the same prepare driven by veon_two_hot_window's per-pixel windows
@@ -393,16 +427,15 @@ int veon_lss_prepare_cameras_twohot(
     int *ranks_depth, int *ranks_feat, int *interval_starts, int *interval_lengths,
     int *plan, int *vstart, int *counts, const int *win, int window_slots, void *stream);
 
-int veon_lss_prepare(int B, int N, int D, int H, int W, const float *coor,
-                     const float *xs, const float *ys, const float *ds,
-                     const float *post_rots_inv, const float *post_trans,
-                     const float *combine, const float *trans, const float *bda,
-                     const float *grid_lower, const float *grid_interval,
-                     const float *grid_size, int64_t voxels_per_batch,
-                     void *workspace, int64_t workspace_bytes, int *ranks_bev,
-                     int *ranks_depth, int *ranks_feat, int *interval_starts,
-                     int *interval_lengths, int *plan, int *counts,
-                     void *stream);
+/*
+ * AlignNetOcc3D.prepare_meta (align_net_occ3d.py:328-352) for one frame: out[b,n] =
+ * inverse(ego2global[b,0]) @ ego2global[b,n] @ sensor2ego[b,n], (B,N,4,4) fp32 in and
+ * out, the algebra in double precision (the reference casts to double, too).
+ */
+int veon_sensor2keyego(int B, int N, const float *sensor2ego, const float *ego2global,
+                       float *out, void *stream);
+
+/* ======== depth_ops.hip ============================================================= */
 
 /*
  * Depth preparation (LSSViewTransformerRaw.downsample_depth /
@@ -420,6 +453,7 @@ int veon_downsample_depth(int BN, int H, int W, int ds, const float *depths,
 int veon_two_hot_depth(int BN, int H, int W, int ds, int D, float lo, float step,
                        float gamma, const float *depths, float *out,
                        void *stream);
+
 /*
  * The same distribution in its compact, EXACT form (the
  * (BN,D,H,W) tensor is never written).  A pixel's D+1 logits are -gamma*|d - c_k|
@@ -442,6 +476,8 @@ int veon_two_hot_window_slots(int D, float step, float gamma);
 int veon_two_hot_window(int BN, int H, int W, int ds, int D, float lo, float step,
                         float gamma, float eps, int K, const float *depths, int *win,
                         float *wts, void *stream);
+
+/* ======== vit_block.hip ============================================================= */
 
 /*
  * ViT encoder block kernels (bf16 operands on MFMA, fp32 accumulate, fp32
@@ -474,23 +510,7 @@ int veon_two_hot_window(int BN, int H, int W, int ds, int D, float lo, float ste
  *                      gives NaN there).  Any pattern of masked 64-key tiles is
  *                      exact, however far below zero the live scores lie.
  */
-/* experiment knob of tools/gemm_bench.py: force the tile configuration of
- * veon_vit_gemm (-1 = automatic, 0 = small-tile kernel, 1..6 = ring-kernel tiles) */
-void veon_gemm_ring_set(int config);
-/* Force the small-tile kernel's shape (wm waves down, wn across, mt 16-row blocks per
- * wave) of veon_vit_gemm when it takes that kernel (veon_gemm_ring_set(0) sends every
- * shape there); overrides the VEON_GEMM_SMALL=wm,wn,mt knob of tools/gemm_bench.py.
- * Instantiated: (4,2,1) (4,2,2) (4,4,1) (4,4,2) (8,2,1); any other triple returns
- * VEON_ERR_BAD_ARG and changes nothing.  wm = -1: back to automatic. */
-int veon_gemm_small_set(int wm, int wn, int mt);
 int veon_vit_cast_bf16(const float *in, void *out_bf16, int64_t n, void *stream);
-/* Patch embedding (dinov2_layers/patch_embed.py: Conv2d(kernel = stride = patch)) as a
- * GEMM operand: img fp32 (B,C,H,W) -> bf16 rows [B*(skip + h*w)][kpad], row element
- * c*patch*patch + i*patch + j (the conv weight's order), zero beyond C*patch*patch,
- * ``skip`` zero rows in front of every image (class-token slot).  A remainder of H/W
- * modulo patch is not read (as the convolution). */
-int veon_vit_patchify(const float *img, void *out_bf16, int B, int C, int H, int W,
-                      int patch, int skip, int kpad, void *stream);
 int veon_vit_layernorm(const float *x, const float *gamma, const float *beta,
                        void *out_bf16, int T, int d, float eps, void *stream);
 int veon_vit_gemm(const void *a_bf16, const void *w_bf16, const float *bias,
@@ -509,23 +529,29 @@ int veon_vit_attention_log2(const void *qkv_bf16, const float *bias,
                             void *out_bf16, int B, int T, int H, int head_dim,
                             void *stream);
 
+/* Patch embedding (dinov2_layers/patch_embed.py: Conv2d(kernel = stride = patch)) as a
+ * GEMM operand: img fp32 (B,C,H,W) -> bf16 rows [B*(skip + h*w)][kpad], row element
+ * c*patch*patch + i*patch + j (the conv weight's order), zero beyond C*patch*patch,
+ * ``skip`` zero rows in front of every image (class-token slot).  A remainder of H/W
+ * modulo patch is not read (as the convolution). */
+int veon_vit_patchify(const float *img, void *out_bf16, int B, int C, int H, int W,
+                      int patch, int skip, int kpad, void *stream);
+
 /*
- * The fused pool + max-pool writing straight into the Conv3d body's input: the
- * interior of the zero-padded channels-last bf16 grid [B][Z/dz+2][Y/dy+2][X/dx+2][C]
- * (see veon_conv3d_k3_bf16; allocate it zeroed once, the halo is never
- * written).  Values are the fp32 results of veon_bev_pool_v2_fwd_maxpool_ex
- * rounded to bf16 -- what veon_volume_pack_bf16 of that tensor would store.
+ * Split-K form of the residual GEMM (resid += gamma * (a @ w^T + bias)) for fc2-shaped
+ * problems (long K, few output columns: M = 5406, N = 768 / 1024, K = 3072 / 4096): two
+ * workgroups per output tile take half of K each, the first to finish parks its fp32
+ * accumulators in `slab`, the second adds them to its own and runs the epilogue
+ * (deterministic: a + b is commutative).  veon_vit_gemm_splitk_plan -> slab bytes needed
+ * (0: the shape is not split).  sync_words (2 ints per tile): ZERO on entry, left zero.
+ * veon_vit_block uses it for fc2 with its (by then free) qkv buffer as the slab; the
+ * block workspace therefore has to be ZERO when first used (it ends in the sync words).
  */
-int veon_bev_pool_v2_fwd_maxpool_padded(int c, int n_intervals, int batch, int Z,
-                                        int Y, int X, int dz, int dy, int dx,
-                                        const float *depth, const void *feat,
-                                        int feat_dtype, const int *ranks_depth,
-                                        const int *ranks_feat,
-                                        const int *ranks_bev,
-                                        const int *interval_starts,
-                                        const int *interval_lengths,
-                                        const int *row_first,
-                                        void *out_padded_bf16, void *stream);
+int64_t veon_vit_gemm_splitk_plan(int M, int N, int K, int *tile_out);
+int veon_vit_gemm_splitk(const void *a_bf16, const void *w_bf16, const float *bias,
+                         const float *gamma, float *resid, int M, int N, int K,
+                         void *slab, int64_t slab_bytes, int *sync_words,
+                         int64_t sync_ints, void *stream);
 
 /*
  * One whole pre-norm transformer block on the fp32 residual stream x [B*T, d]
@@ -553,27 +579,13 @@ typedef struct veon_vit_block_weights {
   int q_log2;   /* 1: w_qkv / b_qkv's q rows carry head_dim^-0.5 * log2(e) (attention in
                    the exp2 domain, veon_vit_attention_log2); 0: head_dim^-0.5 only */
 } veon_vit_block_weights;
-/*
- * Split-K form of the residual GEMM (resid += gamma * (a @ w^T + bias)) for fc2-shaped
- * problems (long K, few output columns: M = 5406, N = 768 / 1024, K = 3072 / 4096): two
- * workgroups per output tile take half of K each, the first to finish parks its fp32
- * accumulators in `slab`, the second adds them to its own and runs the epilogue
- * (deterministic: a + b is commutative).  veon_vit_gemm_splitk_plan -> slab bytes needed
- * (0: the shape is not split).  sync_words (2 ints per tile): ZERO on entry, left zero.
- * veon_vit_block uses it for fc2 with its (by then free) qkv buffer as the slab; the
- * block workspace therefore has to be ZERO when first used (it ends in the sync words).
- */
-int64_t veon_vit_gemm_splitk_plan(int M, int N, int K, int *tile_out);
-int veon_vit_gemm_splitk(const void *a_bf16, const void *w_bf16, const float *bias,
-                         const float *gamma, float *resid, int M, int N, int K,
-                         void *slab, int64_t slab_bytes, int *sync_words,
-                         int64_t sync_ints, void *stream);
 int64_t veon_vit_block_workspace_bytes(int B, int T, int d, int mlp_dim);
 int veon_vit_block(float *x, const veon_vit_block_weights *w,
                    const float *attn_bias, int64_t bias_batch_stride,
                    int64_t bias_head_stride, void *workspace,
                    int64_t workspace_bytes, int B, int T, int d, int H,
                    void *stream);
+
 /*
  * LayerNorm of PADDED rows: x fp32 [T, ld], the token is the first d columns (the rest
  * is padding up to the multiples of 64 the GEMM kernels need); statistics over d,
@@ -587,6 +599,28 @@ int veon_vit_layernorm_padded(const float *x, const float *gamma, const float *b
                               void *out_bf16, int T, int d, int ld, float eps,
                               void *stream);
 
+/* nn.LayerNorm over the last dim, fp32 in -> fp32 out, rows of d floats
+ * (d % 128 == 0, d <= 1024): the token LayerNorms (ln_3 / ln_4 / pre_norm) of the
+ * HSA network's blocks (highres_side_adaptor.py:108-135, 138-193). */
+int veon_layernorm_f32(const float *x, const float *gamma, const float *beta,
+                       float *out, int T, int d, float eps, void *stream);
+/* LayerNorm(x + offset) of (B, L, d) fp32 tokens, where offset is the nearest-neighbour
+ * resize (F.interpolate default mode: src = min(floor(dst * in / out), in - 1), the scale
+ * in fp32) of a coarser map `add` [B][h*w][d] fp32 to the Y x X token map, added to the
+ * LAST Y*X tokens of every sample: the tail of HighresSideAdaptorBlock.forward
+ * (highres_side_adaptor.py:123-135 -- neck_add, interpolate, cat / add, ln_4) in one
+ * pass instead of upsample + add + cat + LayerNorm. */
+int veon_layernorm_f32_add_nearest(const float *x, const float *add, const float *gamma,
+                                   const float *beta, float *out, int B, int L, int d,
+                                   int Y, int X, int h, int w, float eps, void *stream);
+/* the same LayerNorm of (B, Y*X, d) fp32 tokens, written as bf16 into the interior
+ * of a zero-haloed channels-last image [B][Y+2][X+2][d] (halo untouched): ln_3
+ * followed by the ConvBlock's permute / reshape to a feature map (:113-122, :38-40). */
+int veon_layernorm_f32_to_padded(const float *x, const float *gamma, const float *beta,
+                                 void *out_padded, int B, int Y, int X, int d,
+                                 float eps, void *stream);
+
+/* ======== conv3d.hip ================================================================ */
 
 /*
  * ---- 3x3x3 Conv3d body of the 3D alignment network ----
@@ -611,6 +645,7 @@ int veon_conv3d_k3_bf16(const void *in_padded, const void *w_bf16,
                         const float *scale, const float *shift,
                         const void *resid_padded, void *out_padded, int B, int Z,
                         int Y, int X, int Cin, int Cout, int relu, void *stream);
+
 /*
  * The 2-D case: 3x3 stride-1 pad-1 convolution on images in the padded
  * channels-last bf16 grid [B][Y+2][X+2][C] (no z halo), same kernel with 9 taps,
@@ -619,21 +654,11 @@ int veon_conv3d_k3_bf16(const void *in_padded, const void *w_bf16,
  * (mmdet3d/models/depth_anything/dpt.py:39-150, util/blocks.py) when the head
  * runs in bf16.
  */
-/* experiment knob of tools/body_bench.py (ablations of the conv kernels' loads;
- * non-zero flags give WRONG results): 0 = normal.  Correct-result bits: 8 (bit 3) takes
- * the general kernel instead of the slab-sharing one; bits 16..27 force the tile (wm, wn,
- * mt: four bits each) -- while they name a tile that is not instantiated, the conv
- * entry points return VEON_ERR_BAD_ARG. */
-void veon_conv_debug_set(int flags);
-/* Host-only: the (rows | cols << 16) tile the conv launcher picks for a problem
- * (kd = 3: veon_conv3d_k3_bf16 on B x Z x Y x X voxels; kd = 1: the 2-D convs on
- * B x Y x X output pixels, stride 1 or 2); -1 for an unsupported shape.  Lets the CPU
- * tests pin the selection rule (csrc/conv3d.hip: conv_pick_tile). */
-int veon_conv_tile_choice(int kd, int B, int Z, int Y, int X, int Cin, int Cout, int stride);
 int veon_conv2d_k3_bf16(const void *in_padded, const void *w_bf16,
                         const float *scale, const float *shift,
                         const void *resid_padded, void *out_padded, int B, int Y,
                         int X, int Cin, int Cout, int relu, void *stream);
+
 /* The same with two optional extras of the epilogue (NULL = absent): a SECOND residual
  * image resid2 (added before the activation) and a second output out_relu that receives
  * relu(result) (not `out_padded` itself).  FeatureFusionBlock (util/blocks.py:86-148)
@@ -654,6 +679,13 @@ int veon_conv2d_k3s2_bf16(const void *in_padded, const void *w_bf16, const float
                           const float *shift, const void *resid_padded, void *out_padded,
                           int B, int Yin, int Xin, int Cin, int Cout, int act,
                           void *stream);
+
+/* Host-only: the (rows | cols << 16) tile the conv launcher picks for a problem
+ * (kd = 3: veon_conv3d_k3_bf16 on B x Z x Y x X voxels; kd = 1: the 2-D convs on
+ * B x Y x X output pixels, stride 1 or 2); -1 for an unsupported shape.  Lets the CPU
+ * tests pin the selection rule (csrc/conv3d.hip: conv_pick_tile). */
+int veon_conv_tile_choice(int kd, int B, int Z, int Y, int X, int Cin, int Cout, int stride);
+
 /* (B,C,Y,X) fp32 or bf16 (nchw_is_bf16) <-> interior of the padded image grid */
 int veon_image_pack_bf16(const void *nchw, int nchw_is_bf16, void *padded, int B,
                          int C, int Y, int X, void *stream);
@@ -664,38 +696,7 @@ int veon_image_unpack(const void *padded, void *nchw, int nchw_is_bf16, int B,
 int veon_image_resize_bilinear(const void *in_padded, void *out_padded, int B,
                                int C, int Yi, int Xi, int Yo, int Xo,
                                void *stream);
-/* Tail of the occupancy path in one kernel (semantic_net/san_in_veon_temporal.py:
- * 196-211 + detectors/veon_temporal.py:219-227): sem (B,Q,zi,yi,xi) and bin
- * (B,2,zi,yi,xi) fp32 logits, each addressed through five ELEMENT strides
- * {b, c, z, y, x} (so the channels-last rows of the heads' GEMMs are read in place),
- * are upsampled trilinearly (align_corners=False) to (Zo,Yo,Xo):
- *   sem_out (B,Q,Zo,Yo,Xo), bin_out (B,2,Zo,Yo,Xo) fp32 contiguous,
- *   cls_out (B,Xo,Yo,Zo) int64 = argmax_c softmax(sem_out) where
- *     softmax(bin_out)[0] > 0.5 (and the best score > 0), else Q (= free). */
-int veon_occ_classify(const float *sem, const int64_t *sem_strides, int Q,
-                      const float *bin, const int64_t *bin_strides, int B, int zi,
-                      int yi, int xi, int Zo, int Yo, int Xo, float *sem_out,
-                      float *bin_out, int64_t *cls_out, void *stream);
-/* Open-vocabulary point retrieval, the `retrieval=True` branch of
- * VEONTemporal.simple_test (detectors/veon_temporal.py:232-241, 331-356;
- * semantic_net/san_in_veon_temporal.py:195-200, 212, 268-273), without forming the
- * upsampled feature volume.  feat (B,C,zi,yi,xi): feat_is_half = 1 -> the half type
- * of the build (e.g. the channels-last interior of a padded volume), 0 -> fp32; both
- * addressed through five ELEMENT strides {b, c, z, y, x} (>= 0).  bin (B,2,zi,yi,xi)
- * fp32, any strides.  points: P int32 triples (x, y, z) in the grid (Zo,Yo,Xo), all
- * of batch element `batch` (datasets/pipelines/loading.py:990-1012).  emb (Q,C) fp32
- * contiguous prompt embeddings; emb_norms: a workspace of Q floats.  For every point
- * p and prompt q, with f = trilinear (align_corners=False) upsample of feat at p:
- *   score[q*P + p] = f.e_q / (max(|f|, 1e-8) * max(|e_q|, 1e-8))
- *   bin_prob[p]    = softmax(upsampled bin at p)[0]     (bin_prob NULL: skipped)
- * Points outside the grid get NaN; nothing is read for them.  1 <= C <= 1024, Q >= 1;
- * channels-last rows must hold C channels (C <= x stride).  No atomics: repeated calls
- * are bit-identical. */
-int veon_occ_retrieve(const void *feat, int feat_is_half, const int64_t *feat_strides,
-                      int C, const float *bin, const int64_t *bin_strides, int B, int zi,
-                      int yi, int xi, int Zo, int Yo, int Xo, const int *points, int P,
-                      int batch, const float *emb, int Q, float *emb_norms, float *score,
-                      float *bin_prob, void *stream);
+
 /* ViT token rows -> padded image, with the pixel shuffle of a ConvTranspose2d(k = s,
  * stride = s) folded in (DPTHead.resize_layers[0:2], depth_anything/dpt.py:55-72:
  * the transposed convolution itself is a GEMM over the tokens whose output row holds
@@ -714,36 +715,7 @@ int veon_image_subsample(const void *in_padded, void *out_padded, int B, int C, 
  * act 0 none / 1 ReLU / 2 sigmoid (the tail of DPTHead.output_conv2, dpt.py). */
 int veon_image_dot(const void *in_padded, const float *w, float bias, float *out,
                    int B, int C, int Y, int X, int act, void *stream);
-/* Physically contiguous device memory (hipExtMallocWithFlags +
- * hipDeviceMallocContiguous) for the lift's output volume, whose write pattern
- * (C planes 4*Z*Y*X bytes apart per workgroup) is sensitive to the page-table
- * fragment size; VEON_ERR_LAUNCH when the driver cannot provide it (the caller
- * then keeps an ordinary allocation).  No reference counterpart: the reference
- * lets torch.zeros allocate the volume (bev_pool.py:17-19). */
-int veon_alloc_contiguous(void **ptr, int64_t bytes);
-/* the same with any hipExtMallocWithFlags flag (probe tool) */
-int veon_alloc_device_flags(void **ptr, int64_t bytes, unsigned flags);
-int veon_free_device(void *ptr);
-/* nn.LayerNorm over the last dim, fp32 in -> fp32 out, rows of d floats
- * (d % 128 == 0, d <= 1024): the token LayerNorms (ln_3 / ln_4 / pre_norm) of the
- * HSA network's blocks (highres_side_adaptor.py:108-135, 138-193). */
-int veon_layernorm_f32(const float *x, const float *gamma, const float *beta,
-                       float *out, int T, int d, float eps, void *stream);
-/* LayerNorm(x + offset) of (B, L, d) fp32 tokens, where offset is the nearest-neighbour
- * resize (F.interpolate default mode: src = min(floor(dst * in / out), in - 1), the scale
- * in fp32) of a coarser map `add` [B][h*w][d] fp32 to the Y x X token map, added to the
- * LAST Y*X tokens of every sample: the tail of HighresSideAdaptorBlock.forward
- * (highres_side_adaptor.py:123-135 -- neck_add, interpolate, cat / add, ln_4) in one
- * pass instead of upsample + add + cat + LayerNorm. */
-int veon_layernorm_f32_add_nearest(const float *x, const float *add, const float *gamma,
-                                   const float *beta, float *out, int B, int L, int d,
-                                   int Y, int X, int h, int w, float eps, void *stream);
-/* the same LayerNorm of (B, Y*X, d) fp32 tokens, written as bf16 into the interior
- * of a zero-haloed channels-last image [B][Y+2][X+2][d] (halo untouched): ln_3
- * followed by the ConvBlock's permute / reshape to a feature map (:113-122, :38-40). */
-int veon_layernorm_f32_to_padded(const float *x, const float *gamma, const float *beta,
-                                 void *out_padded, int B, int Y, int X, int d,
-                                 float eps, void *stream);
+
 /* LayerNorm over the channels of every pixel of a padded channels-last bf16 image:
  * the nn.LayerNorm calls of ConvBlock.forward (highres_side_adaptor.py:31-52) with
  * their permute / reshape pairs.  out_tokens_f32 = 0: out is a padded bf16 image of
@@ -755,6 +727,16 @@ int veon_image_layernorm_bf16(const void *in_padded, const float *gamma,
                               const float *beta, void *out, int out_tokens_f32, int B,
                               int C, int Y, int X, float eps, const float *resid_tokens,
                               void *stream);
+
+/* (B,C,Z,Y,X) fp32 <-> interior of the padded channels-last bf16 grid (the halo
+ * is not touched: allocate the grid zeroed once). */
+int veon_volume_pack_bf16(const float *ncdhw, void *padded, int B, int C, int Z,
+                          int Y, int X, void *stream);
+int veon_volume_unpack_f32(const void *padded, float *ncdhw, int B, int C, int Z,
+                           int Y, int X, void *stream);
+
+/* ======== temporal.hip ============================================================== */
+
 /* ---- temporal path, csrc/temporal.hip ---------------------
  * Sampling + attention core of TemporalDeformable.forward
  * (mmdet3d/models/semantic_net/side_adapter/align_net_occ3d.py:138-196), replacing
@@ -787,12 +769,87 @@ int veon_warp_affine(const float *cur2glob, const float *prev2glob, int mat_stri
  * shift there and a 3x3x3 conv is to consume it). */
 int veon_volume_zero_halo_bf16(void *padded, int B, int C, int Z, int Y, int X,
                                void *stream);
-/* (B,C,Z,Y,X) fp32 <-> interior of the padded channels-last bf16 grid (the halo
- * is not touched: allocate the grid zeroed once). */
-int veon_volume_pack_bf16(const float *ncdhw, void *padded, int B, int C, int Z,
-                          int Y, int X, void *stream);
-int veon_volume_unpack_f32(const void *padded, float *ncdhw, int B, int C, int Z,
-                           int Y, int X, void *stream);
+
+/* ======== occ_head.hip ============================================================== */
+
+/* Tail of the occupancy path in one kernel (semantic_net/san_in_veon_temporal.py:
+ * 196-211 + detectors/veon_temporal.py:219-227): sem (B,Q,zi,yi,xi) and bin
+ * (B,2,zi,yi,xi) fp32 logits, each addressed through five ELEMENT strides
+ * {b, c, z, y, x} (so the channels-last rows of the heads' GEMMs are read in place),
+ * are upsampled trilinearly (align_corners=False) to (Zo,Yo,Xo):
+ *   sem_out (B,Q,Zo,Yo,Xo), bin_out (B,2,Zo,Yo,Xo) fp32 contiguous,
+ *   cls_out (B,Xo,Yo,Zo) int64 = argmax_c softmax(sem_out) where
+ *     softmax(bin_out)[0] > 0.5 (and the best score > 0), else Q (= free). */
+int veon_occ_classify(const float *sem, const int64_t *sem_strides, int Q,
+                      const float *bin, const int64_t *bin_strides, int B, int zi,
+                      int yi, int xi, int Zo, int Yo, int Xo, float *sem_out,
+                      float *bin_out, int64_t *cls_out, void *stream);
+
+/* ======== occ_retrieval.hip ========================================================= */
+
+/* Open-vocabulary point retrieval, the `retrieval=True` branch of
+ * VEONTemporal.simple_test (detectors/veon_temporal.py:232-241, 331-356;
+ * semantic_net/san_in_veon_temporal.py:195-200, 212, 268-273), without forming the
+ * upsampled feature volume.  feat (B,C,zi,yi,xi): feat_is_half = 1 -> the half type
+ * of the build (e.g. the channels-last interior of a padded volume), 0 -> fp32; both
+ * addressed through five ELEMENT strides {b, c, z, y, x} (>= 0).  bin (B,2,zi,yi,xi)
+ * fp32, any strides.  points: P int32 triples (x, y, z) in the grid (Zo,Yo,Xo), all
+ * of batch element `batch` (datasets/pipelines/loading.py:990-1012).  emb (Q,C) fp32
+ * contiguous prompt embeddings; emb_norms: a workspace of Q floats.  For every point
+ * p and prompt q, with f = trilinear (align_corners=False) upsample of feat at p:
+ *   score[q*P + p] = f.e_q / (max(|f|, 1e-8) * max(|e_q|, 1e-8))
+ *   bin_prob[p]    = softmax(upsampled bin at p)[0]     (bin_prob NULL: skipped)
+ * Points outside the grid get NaN; nothing is read for them.  1 <= C <= 1024, Q >= 1;
+ * channels-last rows must hold C channels (C <= x stride).  No atomics: repeated calls
+ * are bit-identical. */
+int veon_occ_retrieve(const void *feat, int feat_is_half, const int64_t *feat_strides,
+                      int C, const float *bin, const int64_t *bin_strides, int B, int zi,
+                      int yi, int xi, int Zo, int Yo, int Xo, const int *points, int P,
+                      int batch, const float *emb, int Q, float *emb_norms, float *score,
+                      float *bin_prob, void *stream);
+
+/* ======== memory.hip ================================================================ */
+
+/* Physically contiguous device memory (hipExtMallocWithFlags +
+ * hipDeviceMallocContiguous) for the lift's output volume, whose write pattern
+ * (C planes 4*Z*Y*X bytes apart per workgroup) is sensitive to the page-table
+ * fragment size; VEON_ERR_LAUNCH when the driver cannot provide it (the caller
+ * then keeps an ordinary allocation).  No reference counterpart: the reference
+ * lets torch.zeros allocate the volume (bev_pool.py:17-19). */
+int veon_alloc_contiguous(void **ptr, int64_t bytes);
+/* the same with any hipExtMallocWithFlags flag (probe tool) */
+int veon_alloc_device_flags(void **ptr, int64_t bytes, unsigned flags);
+int veon_free_device(void *ptr);
+
+/* ======== experiment setters ======================================================== */
+/* Knobs of the tools and of the tile-forcing tests, defined in bev_pool_rows.hip,
+ * vit_block.hip and conv3d.hip; the product path never calls them. */
+
+/* experiment knob of tools/poolbench.py / tools/xcd_order_ab.py; 0 = production.
+ * bits 0-3: ablations of the row max-pool kernel (results invalid); bit 4: tile =
+ * blockIdx instead of the XCD-grouped tile order; bits 8-11: (lg + 1) forces runs of
+ * 2^lg tiles per XCD -- the order never changes a result. */
+void veon_pool_debug_set(int flags);
+/* tuning knobs of the row max-pool kernel (0 = built-in default): worker
+ * workgroups, longest cold list, longest warm list */
+void veon_pool_tune_set(int workers, int cold_max, int warm_max);
+
+/* experiment knob of tools/gemm_bench.py: force the tile configuration of
+ * veon_vit_gemm (-1 = automatic, 0 = small-tile kernel, 1..6 = ring-kernel tiles) */
+void veon_gemm_ring_set(int config);
+/* Force the small-tile kernel's shape (wm waves down, wn across, mt 16-row blocks per
+ * wave) of veon_vit_gemm when it takes that kernel (veon_gemm_ring_set(0) sends every
+ * shape there); overrides the VEON_GEMM_SMALL=wm,wn,mt knob of tools/gemm_bench.py.
+ * Instantiated: (4,2,1) (4,2,2) (4,4,1) (4,4,2) (8,2,1); any other triple returns
+ * VEON_ERR_BAD_ARG and changes nothing.  wm = -1: back to automatic. */
+int veon_gemm_small_set(int wm, int wn, int mt);
+
+/* experiment knob of tools/body_bench.py (ablations of the conv kernels' loads;
+ * non-zero flags give WRONG results): 0 = normal.  Correct-result bits: 8 (bit 3) takes
+ * the general kernel instead of the slab-sharing one; bits 16..27 force the tile (wm, wn,
+ * mt: four bits each) -- while they name a tile that is not instantiated, the conv
+ * entry points return VEON_ERR_BAD_ARG. */
+void veon_conv_debug_set(int flags);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,41 @@ def test_library_exports_every_declared_symbol():
         assert lib.veon_half_mode() == (1 if flavour == 'fp16' else 0)
 
 
+def test_binding_reads_its_signatures_from_the_header(tmp_path):
+    """The ctypes table is parsed from include/veon_hip.h: pin the parser with
+    prototypes of every kind the header has, written out as literal ctypes lists."""
+    vp, ci, i64, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    sig = _lib._SIGNATURES
+    assert len(sig) == len(_header_symbols())
+    assert sig['veon_abi_version'] == (ci, [])
+    assert sig['veon_status_string'] == (ctypes.c_char_p, [ci])
+    assert sig['veon_pool_debug_set'] == (None, [ci])
+    assert sig['veon_vit_block_workspace_bytes'] == (i64, [ci, ci, ci, ci])
+    # void **, int64_t, unsigned
+    assert sig['veon_alloc_device_flags'] == (ci, [vp, i64, ctypes.c_uint])
+    # const double * host pointers
+    assert sig['veon_warp_affine'] == (ci, [vp, vp, ci, vp, vp, vp, ci, vp])
+    # struct pointer, two int64_t strides, int64_t workspace size
+    assert sig['veon_vit_block'] == (ci, [vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, ci, vp])
+    # five ints, four floats, one int, four pointers (the last: the stream)
+    assert sig['veon_two_hot_window'] == (ci, [ci, ci, ci, ci, ci, cf, cf, cf, cf, ci,
+                                               vp, vp, vp, vp])
+    assert sig['veon_two_hot_window_slots'] == (ci, [ci, cf, cf])
+    # a prototype that spans lines and mixes every scalar kind with pointers
+    assert sig['veon_bev_pool_v2_fwd_rows'] == (ci, [ci, ci, i64, vp, vp, ci, vp, vp, vp, vp,
+                                                     i64, i64, ci, vp])
+    # what the loaded library carries is this table
+    fn = _lib.lib().veon_alloc_device_flags
+    assert (fn.restype, list(fn.argtypes)) == sig['veon_alloc_device_flags']
+    # a declaration outside the header's style is an error that quotes it, never a default
+    for bad in ('int veon_x(size_t n);', 'long veon_x(int n);', 'int veon_x(int n, ...);',
+                'int veon_x(int a); int veon_x(int a);', 'static int veon_y = 3;'):
+        h = tmp_path / 'bad.h'
+        h.write_text('/* c */\nint veon_ok(const float *p, void *stream);\n' + bad + '\n')
+        with pytest.raises(_lib.VeonHipError, match='veon_[xy]'):
+            _lib._parse_header(str(h))
+
+
 def test_half_flavour_switch():
     from veon_amd import half
     assert half.dtype() == torch.bfloat16 and half.name() == 'bf16'   # default

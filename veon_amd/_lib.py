@@ -8,10 +8,12 @@ the ops are hipGraph-capturable and race-free against surrounding torch ops
 """
 import ctypes
 import os
+import re
 
 import torch
 
 from . import half as _half
+from .build import INCLUDE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libveon_hip.so')
@@ -21,13 +23,6 @@ LIB_PATHS = {'bf16': LIB_PATH, 'fp16': os.path.join(_HERE, 'libveon_hip_f16.so')
 if os.environ.get('VEON_HIP_LIB'):
     LIB_PATHS['bf16'] = os.environ['VEON_HIP_LIB']
 _libs = {}  # flavour -> loaded library
-_lib = None
-
-_vp = ctypes.c_void_p
-_ci = ctypes.c_int
-_i64 = ctypes.c_int64
-_cf = ctypes.c_float
-
 
 
 class VitBlockWeights(ctypes.Structure):
@@ -45,95 +40,6 @@ class VitBlockWeights(ctypes.Structure):
                 ('q_log2', ctypes.c_int)]
 
 
-_SIGNATURES = {
-    'veon_abi_version': (_ci, []),
-    'veon_half_mode': (_ci, []),
-    'veon_status_string': (ctypes.c_char_p, [_ci]),
-    'veon_bev_pool_v2_fwd': (_ci, [_ci, _ci] + [_vp] * 8 + [_vp]),
-    'veon_bev_pool_v2_bwd': (_ci, [_ci, _ci] + [_vp] * 10 + [_vp]),
-    'veon_bev_pool_v2_fwd_fused': (_ci, [_ci, _ci, _ci, _i64] + [_vp] * 9 + [_ci, _vp]),
-    'veon_feat_nchw_to_nhwc': (_ci, [_vp, _vp] + [_ci] * 4 + [_vp]),
-    'veon_bev_pool_v2_fwd_fused_strided': (_ci, [_ci, _ci, _ci, _i64, _vp, _vp, _ci] + [_vp] * 7 + [_i64, _vp]),
-    'veon_bev_pool_v2_fwd_fused_ex': (_ci, [_ci, _ci, _ci, _i64, _vp, _vp, _ci] + [_vp] * 7 + [_ci, _vp]),
-    'veon_bev_pool_v2_fwd_maxpool_ex': (_ci, [_ci] * 9 + [_vp, _vp, _ci] + [_vp] * 7 + [_vp]),
-    'veon_bev_pool_v2_fwd_maxpool_padded': (_ci, [_ci] * 9 + [_vp, _vp, _ci] + [_vp] * 7 + [_vp]),
-    'veon_bev_pool_tile_voxels': (_ci, []),
-    'veon_volume_maxpool2_f32': (_ci, [_vp, _vp, _i64] + [_ci] * 3 + [_vp]),
-    'veon_pool_debug_set': (None, [_ci]),
-    'veon_pool_tune_set': (None, [_ci, _ci, _ci]),
-    'veon_bev_pool_voxel_table_ints': (_i64, [_ci, _i64]),
-    'veon_bev_pool_voxel_table': (_ci, [_ci, _ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),
-    'veon_bev_pool_v2_fwd_rows': (_ci, [_ci, _ci, _i64, _vp, _vp, _ci, _vp, _vp, _vp, _vp,
-                                        _i64, _i64, _ci, _vp]),
-    'veon_bev_pool_v2_fwd_rows_maxpool': (_ci, [_ci] * 8 + [_vp, _vp, _ci, _vp, _vp, _vp, _vp,
-                                                _ci, _i64, _vp]),
-    'veon_bev_pool_rows_maxpool_chunk': (_ci, []),
-    'veon_bev_pool_v2_fwd_rows_maxpool_ordered': (_ci, [_ci] * 8 + [_vp, _vp, _ci, _vp, _vp, _vp,
-                                                        _vp, _ci, _i64, _vp, _vp]),
-    'veon_bev_pool_plan_ints': (_i64, [_ci, _i64]),
-    'veon_bev_pool_plan': (_ci, [_ci, _ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),
-    'veon_bev_pool_row_table': (_ci, [_ci, _ci, _ci, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'veon_bev_pool_v2_fwd_maxpool': (_ci, [_ci] * 9 + [_vp] * 9 + [_vp]),
-    'veon_downsample_depth': (_ci, [_ci] * 4 + [_vp, _vp, _vp]),
-    'veon_two_hot_depth': (_ci, [_ci] * 5 + [_cf] * 3 + [_vp, _vp, _vp]),
-    'veon_two_hot_window_slots': (_ci, [_ci, _cf, _cf]),
-    'veon_two_hot_window': (_ci, [_ci] * 5 + [_cf] * 4 + [_ci, _vp, _vp, _vp, _vp]),
-    'veon_gemm_ring_set': (None, [_ci]),
-    'veon_gemm_small_set': (_ci, [_ci, _ci, _ci]),
-    'veon_vit_cast_bf16': (_ci, [_vp, _vp, _i64, _vp]),
-    'veon_vit_layernorm': (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _cf, _vp]),
-    'veon_vit_layernorm_padded': (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _vp]),
-    'veon_vit_patchify': (_ci, [_vp, _vp] + [_ci] * 7 + [_vp]),
-    'veon_vit_gemm': (_ci, [_vp] * 6 + [_ci] * 4 + [_vp]),
-    'veon_vit_attention': (_ci, [_vp, _vp, _i64, _i64, _vp, _ci, _ci, _ci, _ci, _vp]),
-    'veon_vit_attention_log2': (_ci, [_vp, _vp, _i64, _i64, _vp, _ci, _ci, _ci, _ci, _vp]),
-    'veon_vit_block_workspace_bytes': (_i64, [_ci] * 4),
-    'veon_vit_gemm_splitk_plan': (_i64, [_ci, _ci, _ci, _vp]),
-    'veon_vit_gemm_splitk': (_ci, [_vp] * 5 + [_ci] * 3 + [_vp, _i64, _vp, _i64, _vp]),
-    'veon_vit_block': (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _i64] + [_ci] * 4 + [_vp]),
-    'veon_conv3d_guard_rows': (_i64, [_ci, _ci]),
-    'veon_conv_debug_set': (None, [_ci]),
-    'veon_conv_tile_choice': (_ci, [_ci] * 8),
-    'veon_conv3d_k3_bf16': (_ci, [_vp] * 6 + [_ci] * 7 + [_vp]),
-    'veon_conv2d_k3_bf16': (_ci, [_vp] * 6 + [_ci] * 6 + [_vp]),
-    'veon_conv2d_k3_bf16_ex': (_ci, [_vp] * 8 + [_ci] * 6 + [_vp]),
-    'veon_conv2d_k3s2_bf16': (_ci, [_vp] * 6 + [_ci] * 6 + [_vp]),
-    'veon_image_resize_bilinear': (_ci, [_vp, _vp] + [_ci] * 6 + [_vp]),
-    'veon_image_dot': (_ci, [_vp, _vp, _cf, _vp] + [_ci] * 5 + [_vp]),
-    'veon_tokens_to_image': (_ci, [_vp, _i64] + [_ci] * 6 + [_vp, _ci, _vp]),
-    'veon_image_subsample': (_ci, [_vp, _vp] + [_ci] * 5 + [_vp]),
-    'veon_occ_classify': (_ci, [_vp, _vp, _ci, _vp, _vp] + [_ci] * 7 + [_vp, _vp, _vp, _vp]),
-    'veon_occ_retrieve': (_ci, [_vp, _ci, _vp, _ci, _vp, _vp] + [_ci] * 7 + [_vp, _ci, _ci, _vp,
-                                                                            _ci] + [_vp] * 4),
-    'veon_image_pack_bf16': (_ci, [_vp, _ci, _vp] + [_ci] * 4 + [_vp]),
-    'veon_image_unpack': (_ci, [_vp, _vp, _ci] + [_ci] * 4 + [_vp]),
-    'veon_alloc_contiguous': (_ci, [_vp, _i64]),
-    'veon_alloc_device_flags': (_ci, [_vp, _i64, ctypes.c_uint]),
-    'veon_free_device': (_ci, [_vp]),
-    'veon_layernorm_f32': (_ci, [_vp] * 4 + [_ci, _ci, _cf, _vp]),
-    'veon_layernorm_f32_add_nearest': (_ci, [_vp] * 5 + [_ci] * 7 + [_cf, _vp]),
-    'veon_layernorm_f32_to_padded': (_ci, [_vp] * 4 + [_ci] * 4 + [_cf, _vp]),
-    'veon_image_layernorm_bf16': (_ci, [_vp] * 4 + [_ci] * 5 + [_cf, _vp, _vp]),
-    'veon_deform_attention_bf16': (_ci, [_vp] * 4 + [_ci] * 8 + [_vp]),
-    'veon_volume_warp_bf16': (_ci, [_vp] * 3 + [_ci] * 5 + [_vp]),
-    'veon_warp_affine': (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _ci, _vp]),
-    'veon_volume_zero_halo_bf16': (_ci, [_vp] + [_ci] * 5 + [_vp]),
-    'veon_volume_pack_bf16': (_ci, [_vp, _vp] + [_ci] * 5 + [_vp]),
-    'veon_volume_unpack_f32': (_ci, [_vp, _vp] + [_ci] * 5 + [_vp]),
-    'veon_camera_matrices': (_ci, [_ci] + [_vp] * 6 + [_vp]),
-    'veon_sensor2keyego': (_ci, [_ci, _ci, _vp, _vp, _vp, _vp]),
-    'veon_lidar_coor': (_ci, [_ci] * 5 + [_vp] * 9 + [_vp]),
-    'veon_lss_prepare_workspace_bytes': (_i64, [_i64, _i64]),
-    'veon_lss_prepare_cameras': (_ci, [_ci] * 5 + [_vp] * 8 + [_vp] * 3 + [_i64, _vp, _i64, _ci]
-                                 + [_vp] * 8 + [_vp]),
-    'veon_lss_prepare_cameras_sparse': (_ci, [_ci] * 5 + [_vp] * 8 + [_vp] * 3
-                                        + [_i64, _vp, _i64, _ci] + [_vp] * 8 + [_vp, _cf, _vp]),
-    'veon_lss_prepare_cameras_twohot': (_ci, [_ci] * 5 + [_vp] * 8 + [_vp] * 3
-                                        + [_i64, _vp, _i64, _ci] + [_vp] * 8 + [_vp, _ci, _vp]),
-    'veon_lss_prepare': (_ci, [_ci] * 5 + [_vp] * 9 + [_vp] * 3 + [_i64, _vp, _i64]
-                         + [_vp] * 7 + [_vp]),
-}
-
 LAYOUT_BZYXC = 0
 LAYOUT_BCZYX = 1
 FEAT_F32, FEAT_F16, FEAT_BF16 = 0, 1, 2
@@ -143,23 +49,70 @@ class VeonHipError(RuntimeError):
     pass
 
 
+_C_TYPES = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
+            'unsigned': ctypes.c_uint}
+
+
+def _ctype(decl, is_return=False):
+    """ctypes type of one parameter (or of the return type) of a prototype of
+    include/veon_hip.h; ValueError for anything the header's style does not allow."""
+    if '*' in decl:
+        if not is_return:
+            return ctypes.c_void_p
+        if decl.replace(' ', '') == 'constchar*':
+            return ctypes.c_char_p
+        raise ValueError(decl)
+    words = [w for w in decl.split() if w != 'const']
+    if is_return and words == ['void']:
+        return None
+    if not is_return and len(words) == 2:   # type + parameter name
+        words = words[:1]
+    if len(words) == 1 and words[0] in _C_TYPES:
+        return _C_TYPES[words[0]]
+    raise ValueError(decl)
+
+
+def _parse_header(path):
+    """{entry point: (restype, argtypes)} of every prototype ``ret veon_name(args);`` of
+    the header (the style its opening comment states: C89 prototypes of scalar and
+    pointer parameters, one typedef struct).  Every pointer is passed as c_void_p.  A
+    statement that is not such a prototype raises: never a silent default."""
+    with open(path) as f:
+        text = f.read()
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)                        # comments
+    text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)                       # preprocessor
+    text = re.sub(r'extern\s+"C"\s*\{', ' ', text)
+    text = re.sub(r'typedef\s+struct\s+\w*\s*\{.*?\}\s*\w+\s*;', ' ', text, flags=re.S)
+    table = {}
+    for stmt in text.split(';'):
+        stmt = ' '.join(stmt.split())
+        if stmt in ('', '}'):            # '}' closes the extern "C" block
+            continue
+        m = re.fullmatch(r'(.+?)\b(veon_\w+) ?\((.*)\)', stmt)
+        try:
+            if m is None or m.group(2) in table:
+                raise ValueError(stmt)
+            args = m.group(3).strip()
+            argtypes = [] if args == 'void' else [_ctype(a) for a in args.split(',')]
+            table[m.group(2)] = (_ctype(m.group(1), is_return=True), argtypes)
+        except ValueError:
+            raise VeonHipError('%s: the binding cannot read the declaration %r' % (path, stmt))
+    return table
+
+
+# the C ABI, read once per process from the header the library is compiled against
+_SIGNATURES = _parse_header(os.path.join(INCLUDE, 'veon_hip.h'))
+
+
 def declared_symbols():
     """Every entry point include/veon_hip.h declares (checked by the CPU tests)."""
     return sorted(_SIGNATURES)
-
-
-def register(name, restype, argtypes):
-    _SIGNATURES[name] = (restype, argtypes)
-    for loaded in _libs.values():
-        fn = getattr(loaded, name)
-        fn.restype, fn.argtypes = restype, argtypes
 
 
 def lib():
     """The native library of the process's half flavour (veon_amd/half.py):
     libveon_hip.so (bf16 operands) or libveon_hip_f16.so (fp16), the same entry
     points in both; raise (never fall back) when it is absent."""
-    global _lib
     flavour = _half.name()
     loaded = _libs.get(flavour)
     if loaded is None:
@@ -175,7 +128,6 @@ def lib():
         if loaded.veon_half_mode() != (1 if flavour == 'fp16' else 0):
             raise VeonHipError('%s was not built for %s operands' % (path, flavour))
         _libs[flavour] = loaded
-    _lib = loaded
     return loaded
 
 
@@ -250,3 +202,14 @@ def on_device(device):
     if device.index is None or device.index == torch.cuda.current_device():
         return _NO_GUARD
     return torch.cuda.device(device)
+
+
+def launch(name, device, *args):
+    """Call entry point ``name`` on PyTorch's current stream of ``device``: a tensor
+    argument becomes its device address, None becomes NULL, anything else is passed
+    as it is; the stream goes last, as in every kernel entry point of the header."""
+    fn = getattr(lib(), name)
+    cargs = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    with on_device(device):
+        status = fn(*cargs, stream_ptr(device))
+    check(status, name)

@@ -31,9 +31,12 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, '*.hip')))
 
 
+def _headers():
+    return glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(INCLUDE, '*.h'))
+
+
 def _deps():
-    return sources() + glob.glob(os.path.join(CSRC, '*.h')) + \
-        glob.glob(os.path.join(INCLUDE, '*.h'))
+    return sources() + _headers()
 
 
 def up_to_date(flavour=None):
@@ -63,8 +66,7 @@ def _stale(obj, src):
     if not os.path.exists(obj):
         return True
     t = os.path.getmtime(obj)
-    headers = glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(INCLUDE, '*.h'))
-    return any(os.path.getmtime(d) > t for d in [src] + headers)
+    return any(os.path.getmtime(d) > t for d in [src] + _headers())
 
 
 def build(force=False, verbose=False, jobs=None):
@@ -78,7 +80,10 @@ def build(force=False, verbose=False, jobs=None):
     for fl, (lib, objdir, defs) in FLAVOURS.items():
         os.makedirs(os.path.join(HERE, objdir), exist_ok=True)
         todo += [(s, fl) for s in sources() if force or _stale(_obj(s, fl), s)]
-    jobs = jobs or min(len(todo), max(1, (os.cpu_count() or 2) // 2)) or 1
+    # MAX_JOBS when the environment sets it; never more than 16 compilers by default
+    # (os.cpu_count() is the whole machine, not what this process may use)
+    jobs = jobs or int(os.environ.get('MAX_JOBS') or min(16, max(1, (os.cpu_count() or 2) // 2)))
+    jobs = max(1, min(jobs, len(todo)))
     procs, failed = [], False
     pending = list(todo)
     while pending or procs:

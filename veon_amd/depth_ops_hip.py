@@ -12,10 +12,7 @@ def downsample_depth(depths, downsample):
     ds = int(downsample)
     src = depths.contiguous().float()
     out = torch.empty((B, N, H // ds, W // ds), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().veon_downsample_depth(
-            B * N, H, W, ds, _lib.ptr(src), _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_downsample_depth')
+    _lib.launch('veon_downsample_depth', dev, B * N, H, W, ds, src, out)
     return out
 
 
@@ -29,11 +26,8 @@ def two_hot_depth(depths, D, lo, step, gamma=4, fused_downsample=0):
         H, W = H // ds, W // ds
     src = depths.contiguous().float()
     out = torch.empty((B, N, D, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().veon_two_hot_depth(
-            B * N, H, W, ds, D, float(lo), float(step), float(gamma),
-            _lib.ptr(src), _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_two_hot_depth')
+    _lib.launch('veon_two_hot_depth', dev, B * N, H, W, ds, D, float(lo), float(step),
+                float(gamma), src, out)
     return out
 
 
@@ -45,19 +39,15 @@ def two_hot_windows(depths, D, lo, step, gamma=4, eps=0.0, fused_downsample=0):
     ds = int(fused_downsample)
     if ds:
         H, W = H // ds, W // ds
-    L = _lib.lib()
-    K = L.veon_two_hot_window_slots(int(D), float(step), float(gamma))
+    K = _lib.lib().veon_two_hot_window_slots(int(D), float(step), float(gamma))
     if K <= 0 or K != depth_ops.two_hot_window_slots(D, step, gamma):
         raise _lib.VeonHipError('two-hot window slots: native %d, host %d'
                                 % (K, depth_ops.two_hot_window_slots(D, step, gamma)))
     src = depths.contiguous().float()
     win = torch.empty((B, N, H, W, 2), dtype=torch.int32, device=dev)
     wts = torch.empty((B, N, H, W, K), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = L.veon_two_hot_window(
-            B * N, H, W, ds, int(D), float(lo), float(step), float(gamma), float(eps), K,
-            _lib.ptr(src), _lib.ptr(win), _lib.ptr(wts), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_two_hot_window')
+    _lib.launch('veon_two_hot_window', dev, B * N, H, W, ds, int(D), float(lo), float(step),
+                float(gamma), float(eps), K, src, win, wts)
     return depth_ops.TwoHotWindows(win, wts, D, eps)
 
 

@@ -41,12 +41,7 @@ def lidar_coor_from_matrices(frustum, post_rots_inv, post_trans, combine, trans,
     pri, pt, cb, tr, bd = (_f32c(t) for t in (post_rots_inv, post_trans, combine,
                                               trans, bda))
     coor = torch.empty((B, N, D, H, W, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().veon_lidar_coor(
-            B, N, D, H, W, _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(ds),
-            _lib.ptr(pri), _lib.ptr(pt), _lib.ptr(cb), _lib.ptr(tr),
-            _lib.ptr(bd), _lib.ptr(coor), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_lidar_coor')
+    _lib.launch('veon_lidar_coor', dev, B, N, D, H, W, xs, ys, ds, pri, pt, cb, tr, bd, coor)
     return coor
 
 
@@ -58,11 +53,7 @@ def camera_matrices(sensor2ego, cam2imgs, post_rots):
     pri = torch.empty((B, N, 3, 3), dtype=torch.float32, device=dev)
     comb = torch.empty((B, N, 3, 3), dtype=torch.float32, device=dev)
     trans = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().veon_camera_matrices(
-            B * N, _lib.ptr(s2e), _lib.ptr(k), _lib.ptr(pr), _lib.ptr(pri),
-            _lib.ptr(comb), _lib.ptr(trans), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_camera_matrices')
+    _lib.launch('veon_camera_matrices', dev, B * N, s2e, k, pr, pri, comb, trans)
     return pri, comb, trans
 
 
@@ -73,10 +64,7 @@ def sensor2keyego(sensor2ego, ego2global):
     B, N = sensor2ego.shape[:2]
     s2e, e2g = _f32c(sensor2ego), _f32c(ego2global)
     out = torch.empty((B, N, 4, 4), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        st = _lib.lib().veon_sensor2keyego(B, N, _lib.ptr(s2e), _lib.ptr(e2g), _lib.ptr(out),
-                                           _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_sensor2keyego')
+    _lib.launch('veon_sensor2keyego', dev, B, N, s2e, e2g, out)
     return out
 
 
@@ -186,29 +174,16 @@ def prepare_device(dims, coor, geometry, lower, interval, gsize, device):
         out.plan = torch.empty(L.veon_bev_pool_plan_ints(B, vpb),
                                dtype=torch.int32, device=device)
     glo, gstep, gsz = _grid_host(lower, interval, gsize)
-    null = ctypes.c_void_p(0)
     if coor is not None:
-        geo = [null] * 8
-        coor_p = _lib.ptr(coor)
-        keep = (coor,)
+        geo = [None] * 8
     else:
         frustum, pri, pt, cb, tr, bd = geometry
-        xs, ys, ds = _axes(frustum, device)
-        keep = tuple(_f32c(t) for t in (pri, pt, cb, tr, bd)) + (xs, ys, ds)
-        geo = [_lib.ptr(xs), _lib.ptr(ys), _lib.ptr(ds)] + \
-            [_lib.ptr(t) for t in keep[:5]]
-        coor_p = null
-    with torch.cuda.device(device):
-        st = L.veon_lss_prepare(
-            B, N, D, H, W, coor_p, *geo,
-            ctypes.cast(glo, ctypes.c_void_p), ctypes.cast(gstep, ctypes.c_void_p),
-            ctypes.cast(gsz, ctypes.c_void_p), vpb, _lib.ptr(ws), ws_bytes,
-            _lib.ptr(out.ranks_bev), _lib.ptr(out.ranks_depth),
-            _lib.ptr(out.ranks_feat), _lib.ptr(out.interval_starts),
-            _lib.ptr(out.interval_lengths), _lib.ptr(out.plan),
-            _lib.ptr(out.counts), _lib.stream_ptr(device))
-    _lib.check(st, 'veon_lss_prepare')
-    del keep
+        geo = list(_axes(frustum, device)) + [_f32c(t) for t in (pri, pt, cb, tr, bd)]
+    _lib.launch('veon_lss_prepare', device, B, N, D, H, W, coor, *geo,
+                ctypes.cast(glo, ctypes.c_void_p), ctypes.cast(gstep, ctypes.c_void_p),
+                ctypes.cast(gsz, ctypes.c_void_p), vpb, ws, ws_bytes, out.ranks_bev,
+                out.ranks_depth, out.ranks_feat, out.interval_starts, out.interval_lengths,
+                out.plan, out.counts)
     return out
 
 
@@ -228,41 +203,35 @@ def prepare_cameras(frustum, sensor2ego, cam2imgs, post_rots, post_trans, bda, l
     s2e, k, pr, pt, bd = (_f32c(t) for t in (sensor2ego, cam2imgs, post_rots, post_trans,
                                               bda))
     glo, gstep, gsz = _grid_host(lower, interval, gsize)
-    args = (B, N, D, H, W, _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(ds), _lib.ptr(s2e),
-            _lib.ptr(k), _lib.ptr(pr), _lib.ptr(pt), _lib.ptr(bd),
+    args = (B, N, D, H, W, xs, ys, ds, s2e, k, pr, pt, bd,
             ctypes.cast(glo, ctypes.c_void_p), ctypes.cast(gstep, ctypes.c_void_p),
-            ctypes.cast(gsz, ctypes.c_void_p), vpb, _lib.ptr(ws.ws), ws.ws_bytes,
+            ctypes.cast(gsz, ctypes.c_void_p), vpb, ws.ws, ws.ws_bytes,
             0 if ws.dirty else 1,   # hist_is_zero
-            _lib.ptr(ws.ranks_bev), _lib.ptr(ws.ranks_depth), _lib.ptr(ws.ranks_feat),
-            _lib.ptr(ws.interval_starts), _lib.ptr(ws.interval_lengths),
-            _lib.ptr(ws.plan), _lib.ptr(ws.vstart), _lib.ptr(ws.counts))
+            ws.ranks_bev, ws.ranks_depth, ws.ranks_feat, ws.interval_starts,
+            ws.interval_lengths, ws.plan, ws.vstart, ws.counts)
     ws.dirty = True   # cleared below once every launch was accepted
-    with _lib.on_device(dev):
-        if twohot is not None:
-            # two-hot lift by construction: ``twohot`` = depth_ops.TwoHotWindows; the
-            # returned ranks_depth index its compact weight table ``twohot.wts``
-            if (tuple(twohot.shape) != (B, N, D, H, W) or twohot.device != dev
-                    or twohot.win.dtype != torch.int32 or not twohot.win.is_contiguous()
-                    or not twohot.wts.is_contiguous()):
-                raise _lib.VeonHipError(
-                    'two-hot windows of shape %r on %s do not match the frustum %r on %s'
-                    % (tuple(twohot.shape), twohot.device, (B, N, D, H, W), dev))
-            st = _lib.lib().veon_lss_prepare_cameras_twohot(
-                *args, _lib.ptr(twohot.win), int(twohot.K), _lib.stream_ptr(dev))
-            _lib.check(st, 'veon_lss_prepare_cameras_twohot')
-        elif depth_weights is not None and depth_eps > 0.0:
-            # sparse lift: points whose depth weight is below depth_eps are not sorted
-            if (depth_weights.dtype != torch.float32 or not depth_weights.is_contiguous()
-                    or depth_weights.numel() != B * N * D * H * W
-                    or depth_weights.device != dev):
-                raise _lib.VeonHipError('depth_weights must be a contiguous fp32 '
-                                        '(B,N,D,H,W) tensor on the rig\'s device')
-            st = _lib.lib().veon_lss_prepare_cameras_sparse(
-                *args, _lib.ptr(depth_weights), float(depth_eps), _lib.stream_ptr(dev))
-            _lib.check(st, 'veon_lss_prepare_cameras_sparse')
-        else:
-            st = _lib.lib().veon_lss_prepare_cameras(*args, _lib.stream_ptr(dev))
-            _lib.check(st, 'veon_lss_prepare_cameras')
+    if twohot is not None:
+        # two-hot lift by construction: ``twohot`` = depth_ops.TwoHotWindows; the
+        # returned ranks_depth index its compact weight table ``twohot.wts``
+        if (tuple(twohot.shape) != (B, N, D, H, W) or twohot.device != dev
+                or twohot.win.dtype != torch.int32 or not twohot.win.is_contiguous()
+                or not twohot.wts.is_contiguous()):
+            raise _lib.VeonHipError(
+                'two-hot windows of shape %r on %s do not match the frustum %r on %s'
+                % (tuple(twohot.shape), twohot.device, (B, N, D, H, W), dev))
+        _lib.launch('veon_lss_prepare_cameras_twohot', dev, *args, twohot.win,
+                    int(twohot.K))
+    elif depth_weights is not None and depth_eps > 0.0:
+        # sparse lift: points whose depth weight is below depth_eps are not sorted
+        if (depth_weights.dtype != torch.float32 or not depth_weights.is_contiguous()
+                or depth_weights.numel() != B * N * D * H * W
+                or depth_weights.device != dev):
+            raise _lib.VeonHipError('depth_weights must be a contiguous fp32 '
+                                    '(B,N,D,H,W) tensor on the rig\'s device')
+        _lib.launch('veon_lss_prepare_cameras_sparse', dev, *args, depth_weights,
+                    float(depth_eps))
+    else:
+        _lib.launch('veon_lss_prepare_cameras', dev, *args)
     # a call captured into a hipGraph while the workspace was dirty has the memset in
     # the graph; every replay then leaves a zero histogram like any other call
     ws.dirty = False

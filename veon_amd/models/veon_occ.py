@@ -399,10 +399,7 @@ class VeonOccupancyPath(nn.Module):
             vol = vol.contiguous()
             out = torch.empty((b, c, z // 2, y // 2, x // 2), dtype=torch.float32,
                               device=vol.device)
-            with _lib.on_device(vol.device):
-                st = _lib.lib().veon_volume_maxpool2_f32(
-                    _lib.ptr(vol), _lib.ptr(out), b * c, z, y, x, _lib.stream_ptr(vol.device))
-            _lib.check(st, 'veon_volume_maxpool2_f32')
+            _lib.launch('veon_volume_maxpool2_f32', vol.device, vol, out, b * c, z, y, x)
             return out
         return vol.view(b, c, z // dz, dz, y // dy, dy, x // dx, dx).amax(dim=(3, 5, 7))
 

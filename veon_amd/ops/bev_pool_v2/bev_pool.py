@@ -122,11 +122,8 @@ def _rows(feat):
         B, N, H, W, C = feat.shape
         if feat.stride() == (N * C * H * W, C * H * W, W, 1, H * W) and B * N <= 65535:
             out = torch.empty((B, N, H, W, C), dtype=feat.dtype, device=feat.device)
-            with _lib.on_device(feat.device):
-                st = _lib.lib().veon_feat_nchw_to_nhwc(
-                    _lib.ptr(feat), _lib.ptr(out), feat.element_size(), B * N, C, H * W,
-                    _lib.stream_ptr(feat.device))
-            _lib.check(st, 'veon_feat_nchw_to_nhwc')
+            _lib.launch('veon_feat_nchw_to_nhwc', feat.device, feat, out,
+                        feat.element_size(), B * N, C, H * W)
             return out
     return feat.contiguous()
 
@@ -168,15 +165,10 @@ def build_plan(ranks_bev, interval_starts, batch, voxels_per_batch,
     ``interval_starts`` -- do that when the ranks themselves are cached
     (accelerate=True); otherwise it is rebuilt per call (two tiny kernels)."""
     dev = _lib.require_device(ranks_bev, interval_starts)
-    L = _lib.lib()
-    n_ints = L.veon_bev_pool_plan_ints(batch, voxels_per_batch)
+    n_ints = _lib.lib().veon_bev_pool_plan_ints(batch, voxels_per_batch)
     plan = torch.empty(n_ints, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = L.veon_bev_pool_plan(
-            interval_starts.numel(), ranks_bev.numel(), batch,
-            voxels_per_batch, _lib.ptr(ranks_bev), _lib.ptr(interval_starts),
-            _lib.ptr(counts), _lib.ptr(plan), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_plan')
+    _lib.launch('veon_bev_pool_plan', dev, interval_starts.numel(), ranks_bev.numel(),
+                batch, voxels_per_batch, ranks_bev, interval_starts, counts, plan)
     if attach:
         _cache_put(interval_starts, ranks_bev, '_veon_plan', (batch, voxels_per_batch), plan)
     return plan
@@ -188,15 +180,11 @@ def build_voxel_table(ranks_bev, interval_starts, batch, voxels_per_batch,
     ``veon_bev_pool_voxel_table``): vstart[v] = first point of voxel v in the
     rank-sorted arrays, B*vpb + 1 entries."""
     dev = _lib.require_device(ranks_bev, interval_starts)
-    L = _lib.lib()
-    vstart = torch.empty(L.veon_bev_pool_voxel_table_ints(batch, voxels_per_batch),
-                         dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        st = L.veon_bev_pool_voxel_table(
-            interval_starts.numel(), ranks_bev.numel(), batch, voxels_per_batch,
-            _lib.ptr(ranks_bev), _lib.ptr(interval_starts), _lib.ptr(counts),
-            _lib.ptr(vstart), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_voxel_table')
+    n_ints = _lib.lib().veon_bev_pool_voxel_table_ints(batch, voxels_per_batch)
+    vstart = torch.empty(n_ints, dtype=torch.int32, device=dev)
+    _lib.launch('veon_bev_pool_voxel_table', dev, interval_starts.numel(),
+                ranks_bev.numel(), batch, voxels_per_batch, ranks_bev, interval_starts,
+                counts, vstart)
     if attach:
         _cache_put(interval_starts, ranks_bev, '_veon_vstart', (batch, voxels_per_batch),
                    vstart)
@@ -218,6 +206,19 @@ ROWS_MIN_C = 128
 ROWS_MIN_C_MAXPOOL = 64
 
 
+def _check_out(out, shape, dev):
+    if (tuple(out.shape) != shape or out.dtype != torch.float32
+            or not out.is_contiguous() or out.device != dev):
+        raise _lib.VeonHipError('out must be a contiguous fp32 %r tensor on %s'
+                                % (shape, dev))
+
+
+def _check_out_volume(out_volume, shape):
+    if out_volume.shape != shape:
+        raise _lib.VeonHipError('out_volume shape %r does not match the pooled '
+                                'volume' % (out_volume.shape,))
+
+
 def rows_forward(depth, feat, ranks_depth, ranks_feat, vstart, bev_feat_shape,
                  out=None, variant=0):
     """(B,C,Z,Y,X) fp32 volume by the row kernel, from the dense voxel table."""
@@ -227,15 +228,11 @@ def rows_forward(depth, feat, ranks_depth, ranks_feat, vstart, bev_feat_shape,
         raise _lib.VeonHipError('voxel table does not match bev_feat_shape')
     if out is None:
         out = torch.empty((B, C, Z, Y, X), dtype=torch.float32, device=dev)
-    elif (tuple(out.shape) != (B, C, Z, Y, X) or out.dtype != torch.float32
-          or not out.is_contiguous() or out.device != dev):
-        raise _lib.VeonHipError('out must be a contiguous fp32 (B,C,Z,Y,X) tensor')
-    with _lib.on_device(dev):
-        st = _lib.lib().veon_bev_pool_v2_fwd_rows(
-            C, B, Z * Y * X, _lib.ptr(depth), _lib.ptr(feat), _feat_code(feat),
-            _lib.ptr(ranks_depth), _lib.ptr(ranks_feat), _lib.ptr(vstart),
-            _lib.ptr(out), 0, feat.numel(), variant, _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_v2_fwd_rows')
+    else:
+        _check_out(out, (B, C, Z, Y, X), dev)
+    _lib.launch('veon_bev_pool_v2_fwd_rows', dev, C, B, Z * Y * X, depth, feat,
+                _feat_code(feat), ranks_depth, ranks_feat, vstart, out, 0, feat.numel(),
+                variant)
     return out
 
 
@@ -305,9 +302,7 @@ def rows_maxpool(depth, feat, ranks_depth, ranks_feat, vstart, bev_feat_shape, d
     if vstart.numel() != B * Z * Y * X + 1:
         raise _lib.VeonHipError('voxel table does not match bev_feat_shape')
     if out_volume is not None:
-        if out_volume.shape != (B, C, Z // dz, Y // dy, X // dx):
-            raise _lib.VeonHipError('out_volume shape %r does not match the pooled '
-                                    'volume' % (out_volume.shape,))
+        _check_out_volume(out_volume, (B, C, Z // dz, Y // dy, X // dx))
         target, padded, ret = out_volume.rows, 1, out_volume
     else:
         ret = torch.empty((B, C, Z // dz, Y // dy, X // dx), dtype=torch.float32,
@@ -323,13 +318,9 @@ def rows_maxpool(depth, feat, ranks_depth, ranks_feat, vstart, bev_feat_shape, d
                 or chunk_order.device != dev or not chunk_order.is_contiguous()):
             raise _lib.VeonHipError('chunk_order must be a contiguous int32 permutation '
                                     'of %d chunks on %s' % (want, dev))
-    with _lib.on_device(dev):
-        st = _lib.lib().veon_bev_pool_v2_fwd_rows_maxpool_ordered(
-            C, B, Z, Y, X, dz, dy, dx, _lib.ptr(depth), _lib.ptr(feat),
-            _feat_code(feat), _lib.ptr(ranks_depth), _lib.ptr(ranks_feat),
-            _lib.ptr(vstart), _lib.ptr(target), padded, feat.numel(),
-            _lib.ptr(chunk_order), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_v2_fwd_rows_maxpool_ordered')
+    _lib.launch('veon_bev_pool_v2_fwd_rows_maxpool_ordered', dev, C, B, Z, Y, X, dz, dy, dx,
+                depth, feat, _feat_code(feat), ranks_depth, ranks_feat, vstart, target,
+                padded, feat.numel(), chunk_order)
     return ret
 
 
@@ -348,11 +339,8 @@ def _fused_forward(depth, feat, ranks_depth, ranks_feat, ranks_bev,
     dev = _lib.require_device(depth, feat, ranks_depth, ranks_feat, ranks_bev,
                               interval_starts, interval_lengths)
     if out is not None:
-        want = (B, C, Z, Y, X) if layout == _lib.LAYOUT_BCZYX else (B, Z, Y, X, C)
-        if (tuple(out.shape) != want or out.dtype != torch.float32
-                or not out.is_contiguous() or out.device != dev):
-            raise _lib.VeonHipError('out must be a contiguous fp32 %r tensor on %s'
-                                    % (want, dev))
+        _check_out(out, (B, C, Z, Y, X) if layout == _lib.LAYOUT_BCZYX else (B, Z, Y, X, C),
+                   dev)
     elif layout == _lib.LAYOUT_BCZYX:
         out = torch.empty((B, C, Z, Y, X), dtype=torch.float32, device=dev)
     else:
@@ -365,14 +353,9 @@ def _fused_forward(depth, feat, ranks_depth, ranks_feat, ranks_bev,
     if plan is None:
         plan = build_plan(ranks_bev, interval_starts, B, Z * Y * X,
                           attach=False)
-    with _lib.on_device(dev):
-        st = _lib.lib().veon_bev_pool_v2_fwd_fused_ex(
-            C, interval_starts.numel(), B, Z * Y * X, _lib.ptr(depth),
-            _lib.ptr(feat), _feat_code(feat), _lib.ptr(ranks_depth),
-            _lib.ptr(ranks_feat), _lib.ptr(ranks_bev),
-            _lib.ptr(interval_starts), _lib.ptr(interval_lengths),
-            _lib.ptr(plan), _lib.ptr(out), layout, _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_v2_fwd_fused_ex')
+    _lib.launch('veon_bev_pool_v2_fwd_fused_ex', dev, C, interval_starts.numel(), B,
+                Z * Y * X, depth, feat, _feat_code(feat), ranks_depth, ranks_feat, ranks_bev,
+                interval_starts, interval_lengths, plan, out, layout)
     return out
 
 
@@ -498,9 +481,8 @@ def bev_pool_v2_prepared(depth, feat, pre, bev_feat_shape, out=None):
     if pre.batch != B or pre.vpb != Z * Y * X:
         raise _lib.VeonHipError('prepared ranks do not match bev_feat_shape')
     dev = _lib.require_device(depth, feat, pre.ranks_bev)
-    if out is not None and (tuple(out.shape) != (B, C, Z, Y, X) or out.dtype != torch.float32
-                            or not out.is_contiguous() or out.device != dev):
-        raise _lib.VeonHipError('out must be a contiguous fp32 (B,C,Z,Y,X) tensor')
+    if out is not None:
+        _check_out(out, (B, C, Z, Y, X), dev)
     if getattr(pre, 'vstart', None) is not None and _rows_ok(C, feat=feat):
         return rows_forward(depth, feat, pre.ranks_depth, pre.ranks_feat, pre.vstart,
                             bev_feat_shape, out=out)
@@ -516,15 +498,9 @@ def bev_pool_v2_prepared(depth, feat, pre, bev_feat_shape, out=None):
     # variant (42 vs 35 us at S2): estimate it instead -- about 0.3 intervals per
     # frustum point on nuScenes-like rigs (S2: 72.7 k of 249 k, SV: 342 k of 1.49 M).
     n_est = max(1, int(0.3 * pre.interval_starts.numel()))
-    with _lib.on_device(dev):
-        st = _lib.lib().veon_bev_pool_v2_fwd_fused_ex(
-            C, n_est, B, Z * Y * X, _lib.ptr(depth),
-            _lib.ptr(feat), _feat_code(feat), _lib.ptr(pre.ranks_depth),
-            _lib.ptr(pre.ranks_feat), _lib.ptr(pre.ranks_bev),
-            _lib.ptr(pre.interval_starts), _lib.ptr(pre.interval_lengths),
-            _lib.ptr(plan), _lib.ptr(out), _lib.LAYOUT_BCZYX,
-            _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_v2_fwd_fused_ex')
+    _lib.launch('veon_bev_pool_v2_fwd_fused_ex', dev, C, n_est, B, Z * Y * X, depth, feat,
+                _feat_code(feat), pre.ranks_depth, pre.ranks_feat, pre.ranks_bev,
+                pre.interval_starts, pre.interval_lengths, plan, out, _lib.LAYOUT_BCZYX)
     return out
 
 
@@ -535,13 +511,9 @@ def build_row_table(ranks_bev, interval_starts, batch, voxels_per_batch,
     dev = _lib.require_device(ranks_bev, interval_starts)
     n_rows = batch * (voxels_per_batch // row_voxels)
     table = torch.empty(2 * (n_rows + 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().veon_bev_pool_row_table(
-            interval_starts.numel(), ranks_bev.numel(), batch, voxels_per_batch,
-            row_voxels, _lib.ptr(ranks_bev), _lib.ptr(interval_starts),
-            _lib.ptr(counts), _lib.ptr(table), _lib.ptr(table[n_rows + 1:]),
-            _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_row_table')
+    _lib.launch('veon_bev_pool_row_table', dev, interval_starts.numel(), ranks_bev.numel(),
+                batch, voxels_per_batch, row_voxels, ranks_bev, interval_starts, counts,
+                table, table[n_rows + 1:])
     if attach:
         _cache_put(interval_starts, ranks_bev, '_veon_rows',
                    (batch, voxels_per_batch, row_voxels), table)
@@ -578,28 +550,17 @@ def bev_pool_v2_maxpool(depth, feat, ranks_depth, ranks_feat, ranks_bev,
         table = build_row_table(ranks_bev, interval_starts, B, Z * Y * X, X,
                                 counts=counts, attach=False)
     if out_volume is not None:
-        if out_volume.shape != (B, C, Z // dz, Y // dy, X // dx):
-            raise _lib.VeonHipError('out_volume shape %r does not match the pooled '
-                                    'volume' % (out_volume.shape,))
-        with torch.cuda.device(dev):
-            st = _lib.lib().veon_bev_pool_v2_fwd_maxpool_padded(
-                C, interval_starts.numel(), B, Z, Y, X, dz, dy, dx,
-                _lib.ptr(depth), _lib.ptr(feat), _feat_code(feat),
-                _lib.ptr(ranks_depth), _lib.ptr(ranks_feat), _lib.ptr(ranks_bev),
-                _lib.ptr(interval_starts), _lib.ptr(interval_lengths),
-                _lib.ptr(table), _lib.ptr(out_volume.rows), _lib.stream_ptr(dev))
-        _lib.check(st, 'veon_bev_pool_v2_fwd_maxpool_padded')
+        _check_out_volume(out_volume, (B, C, Z // dz, Y // dy, X // dx))
+        _lib.launch('veon_bev_pool_v2_fwd_maxpool_padded', dev, C, interval_starts.numel(),
+                    B, Z, Y, X, dz, dy, dx, depth, feat, _feat_code(feat), ranks_depth,
+                    ranks_feat, ranks_bev, interval_starts, interval_lengths, table,
+                    out_volume.rows)
         return out_volume
     out = torch.empty((B, C, Z // dz, Y // dy, X // dx), dtype=torch.float32,
                       device=dev)
-    with torch.cuda.device(dev):
-        st = _lib.lib().veon_bev_pool_v2_fwd_maxpool_ex(
-            C, interval_starts.numel(), B, Z, Y, X, dz, dy, dx, _lib.ptr(depth),
-            _lib.ptr(feat), _feat_code(feat), _lib.ptr(ranks_depth),
-            _lib.ptr(ranks_feat), _lib.ptr(ranks_bev),
-            _lib.ptr(interval_starts), _lib.ptr(interval_lengths),
-            _lib.ptr(table), _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_v2_fwd_maxpool_ex')
+    _lib.launch('veon_bev_pool_v2_fwd_maxpool_ex', dev, C, interval_starts.numel(), B,
+                Z, Y, X, dz, dy, dx, depth, feat, _feat_code(feat), ranks_depth, ranks_feat,
+                ranks_bev, interval_starts, interval_lengths, table, out)
     return out
 
 

@@ -39,13 +39,8 @@ def bev_pool_v2_forward(depth, feat, out, ranks_depth, ranks_feat, ranks_bev,
                               ranks_bev, interval_lengths, interval_starts)
     c = feat.size(4) if feat.dim() == 5 else feat.size(-1)
     n_intervals = interval_lengths.size(0)
-    with torch.cuda.device(dev):
-        st = _lib.lib().veon_bev_pool_v2_fwd(
-            c, n_intervals, _lib.ptr(depth), _lib.ptr(feat),
-            _lib.ptr(ranks_depth), _lib.ptr(ranks_feat), _lib.ptr(ranks_bev),
-            _lib.ptr(interval_starts), _lib.ptr(interval_lengths),
-            _lib.ptr(out), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_v2_fwd')
+    _lib.launch('veon_bev_pool_v2_fwd', dev, c, n_intervals, depth, feat, ranks_depth,
+                ranks_feat, ranks_bev, interval_starts, interval_lengths, out)
 
 
 def bev_pool_v2_backward(out_grad, depth_grad, feat_grad, depth, feat,
@@ -62,10 +57,6 @@ def bev_pool_v2_backward(out_grad, depth_grad, feat_grad, depth, feat,
                               interval_lengths, interval_starts)
     c = out_grad.size(4) if out_grad.dim() == 5 else out_grad.size(-1)
     n_intervals = interval_lengths.size(0)
-    with torch.cuda.device(dev):
-        st = _lib.lib().veon_bev_pool_v2_bwd(
-            c, n_intervals, _lib.ptr(out_grad), _lib.ptr(depth), _lib.ptr(feat),
-            _lib.ptr(ranks_depth), _lib.ptr(ranks_feat), _lib.ptr(ranks_bev),
-            _lib.ptr(interval_starts), _lib.ptr(interval_lengths),
-            _lib.ptr(depth_grad), _lib.ptr(feat_grad), _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_bev_pool_v2_bwd')
+    _lib.launch('veon_bev_pool_v2_bwd', dev, c, n_intervals, out_grad, depth, feat,
+                ranks_depth, ranks_feat, ranks_bev, interval_starts, interval_lengths,
+                depth_grad, feat_grad)

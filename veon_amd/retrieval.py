@@ -109,13 +109,9 @@ def retrieve_points(feat, bin_low, points, embeddings, occ_size, batch=0):
     s5 = ctypes.c_int64 * 5
     fs = s5(*view.stride())
     bs = s5(*(bin_low.stride() if bin_low is not None else (0,) * 5))
-    with _lib.on_device(dev):
-        st = _lib.lib().veon_occ_retrieve(
-            _lib.ptr(view), is_half, ctypes.cast(fs, ctypes.c_void_p), C, _lib.ptr(bin_low),
-            ctypes.cast(bs, ctypes.c_void_p), B, zi, yi, xi, Zo, Yo, Xo, _lib.ptr(pts), P,
-            batch, _lib.ptr(emb), Q, _lib.ptr(norms), _lib.ptr(score), _lib.ptr(prob),
-            _lib.stream_ptr(dev))
-    _lib.check(st, 'veon_occ_retrieve')
+    _lib.launch('veon_occ_retrieve', dev, view, is_half, ctypes.cast(fs, ctypes.c_void_p), C,
+                bin_low, ctypes.cast(bs, ctypes.c_void_p), B, zi, yi, xi, Zo, Yo, Xo, pts, P,
+                batch, emb, Q, norms, score, prob)
     return score, prob
 
 
