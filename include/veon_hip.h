@@ -298,6 +298,48 @@ int veon_bev_pool_v2_fwd_rows_maxpool_ordered(
     const int *vstart, void *out, int out_padded_bf16, int64_t feat_elems,
     const int *chunk_order, void *stream);
 
+/*
+ * ---- differentiable pool + (2,2,2) block max (training through
+ * LSSViewTransformerRaw.forward, view_transformer_raw.py:537-555, with the backward
+ * of QuickCumsumCuda, bev_pool.py:43-83, folded in) -- neither direction writes the
+ * un-pooled volume.
+ *
+ * veon_bev_pool_v2_fwd_rows_maxpool_winner: veon_bev_pool_v2_fwd_rows_maxpool_ordered
+ *   with fp32 rows (feat_dtype must be VEON_FEAT_F32) and the fp32 (B,C,Z/2,Y/2,X/2)
+ *   output, bit-equal to it, plus `winner` (B,Z/2,Y/2,X/2,C) uint8: the smallest child
+ *   k = (rz*2 + ry)*2 + rx (the '(dz dh dw)' order of view_transformer_raw.py:549-553)
+ *   whose sum equals the block maximum -- the element torch.max(dim=-1) sends the
+ *   gradient to -- or 255 when that child holds no point (its zero wins: the
+ *   gradient goes nowhere).  4-byte aligned.
+ * veon_bev_pool_point_table: pvox[table_len], table_len = B*N*D*H*W: pvox[ranks_depth[p]]
+ *   = ranks_bev[p] for every kept point p, -1 elsewhere.  Needs the lift's layout:
+ *   every kept point has its own ranks_depth (view_transformer_raw.py:268-270).
+ *   Points whose ranks_depth / ranks_bev lie outside [0, table_len) / [0, n_voxels)
+ *   are ignored.  `counts` as in veon_bev_pool_voxel_table (n_points then bounds it).
+ * veon_bev_pool_v2_bwd_rows_maxpool: with m[p,c] = pooled_grad[q(p),c] if
+ *   winner[q(p),c] == child(p) else 0 for the kept points p (q = pooled parent),
+ *     depth_grad[ranks_depth[p]] = sum_c m[p,c] * feat[ranks_feat[p],c]
+ *     feat_grad[r,c] = sum over the points of pixel r, ascending d, of m[p,c] * depth[..]
+ *   for ranks_feat = img*HW + hw, ranks_depth = (img*D + d)*HW + hw
+ *   (view_transformer_raw.py:268-274); n_images = B*N.  pooled_grad is channels-last
+ *   (B,Z/2,Y/2,X/2,C) fp32.  feat_grad (n_images*HW, c) is written everywhere;
+ *   depth_grad must be zero-filled by the caller (as for veon_bev_pool_v2_bwd) and may
+ *   be NULL (not computed).  No atomics: results are bit-reproducible.  c % 4 == 0.
+ */
+int veon_bev_pool_v2_fwd_rows_maxpool_winner(
+    int c, int batch, int Z, int Y, int X, int dz, int dy, int dx, const float *depth,
+    const void *feat, int feat_dtype, const int *ranks_depth, const int *ranks_feat,
+    const int *vstart, void *out, int64_t feat_elems, const int *chunk_order,
+    uint8_t *winner, void *stream);
+int veon_bev_pool_point_table(int n_points, int64_t table_len, int64_t n_voxels,
+                              const int *ranks_depth, const int *ranks_bev,
+                              const int *counts, int *pvox, void *stream);
+int veon_bev_pool_v2_bwd_rows_maxpool(int c, int n_images, int D, int HW, int batch, int Z,
+                                      int Y, int X, const float *pooled_grad,
+                                      const uint8_t *winner, const int *pvox,
+                                      const float *depth, const float *feat,
+                                      float *depth_grad, float *feat_grad, void *stream);
+
 /* ======== lss_prepare.hip =========================================================== */
 
 /*

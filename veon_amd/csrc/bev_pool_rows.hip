@@ -394,14 +394,42 @@ __device__ __forceinline__ float pooled_value(float m, int n_occ, int full) {
   return n_occ < full ? vmax(0.f, m) : m;  // m = -inf when nothing is occupied
 }
 
-template <int FT, int DZ, int DY, int DX, int OUT>
+// ---- winners (WIN = true: the differentiable max-pool) -------------------------
+// Winner of a pooled (voxel, channel): the smallest child k = (rz*DY + ry)*DX + rx
+// whose sum equals the block maximum -- what torch.max(dim=-1) over the flattened
+// '(dz dh dw)' block sends the gradient to (view_transformer_raw.py:549-553).  The
+// running maximum is strict (`v > m`) over the occupied children in ascending k, so
+// `wk` is the first occupied maximal child; a child without points holds an exact
+// zero, has no point to pass a gradient to, and wins as code 255 when it comes first.
+constexpr int kNoWinner = 255;
+
+// smallest child without points (FULL: none); bit `lb + g*(GL+1) + k` of `occ` is set
+// when child g*GL + k holds points (the lane layout of the boundary entries)
+template <int NSEG, int GL>
+__device__ __forceinline__ int first_empty_child(unsigned long long occ, int lb) {
+  int fe = NSEG * GL;
+#pragma unroll
+  for (int q = NSEG * GL - 1; q >= 0; --q)
+    if (!((occ >> (lb + (q / GL) * (GL + 1) + q % GL)) & 1ull)) fe = q;
+  return fe;
+}
+
+// m: maximum over the occupied children (-inf: none), wk: its first child
+__device__ __forceinline__ unsigned winner_code(float m, int wk, int first_empty, int full) {
+  if (first_empty >= full || m > 0.f) return (unsigned)wk;
+  if (m < 0.f) return kNoWinner;                       // the zero of an empty child wins
+  return wk < first_empty ? (unsigned)wk : kNoWinner;  // m == +-0 ties with the empty ones
+}
+
+template <int FT, int DZ, int DY, int DX, int OUT, bool WIN = false>
 __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
     const float* __restrict__ depth, const void* __restrict__ feat,
     const int* __restrict__ ranks_depth, const int* __restrict__ ranks_feat,
     const int* __restrict__ vstart, int c, int batch, int Z, int Y, int X,
     void* __restrict__ outp, int dbg, int kWorkers, int kCold, int kWarm, int order,
-    const int* __restrict__ chunk_order) {
+    const int* __restrict__ chunk_order, unsigned char* __restrict__ winner) {
   constexpr int NSEG = DZ * DY, GL = DX, NE = NSEG * (GL + 1), FULL = DZ * DY * DX;
+  static_assert(!WIN || OUT == 0, "winners go with the fp32 (B,C,Zo,Yo,Xo) output");
   static_assert(NE <= 16, "boundary entries of one pooled voxel must fit 16 lanes");
   if (dbg && (((dbg & 1) && blockIdx.x < kWorkers) || ((dbg & 2) && blockIdx.x >= kWorkers)))
     return;
@@ -501,13 +529,21 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
             const int cc = threadIdx.x;
             float m = kmin;
             int n_occ = 0;
+            [[maybe_unused]] int wk = kNoWinner, fe = FULL;
+#pragma unroll
+            for (int q = FULL - 1; q >= 0; --q)
+              if (WIN && ctab[2 * q + 1] == 0) fe = q;
 #pragma unroll
             for (int q = 0; q < FULL; ++q)
               if (ctab[2 * q + 1] > 0) {
-                m = vmax(m, hkey[q * 256 + cc]);
+                const float sq = hkey[q * 256 + cc];
+                if constexpr (WIN) wk = sq > m ? q : wk;
+                m = vmax(m, sq);
                 ++n_occ;
               }
             const float v = pooled_value(m, n_occ, FULL);
+            if constexpr (WIN)
+              winner[(int64_t)pid * c + c0 + cc] = (unsigned char)winner_code(m, wk, fe, FULL);
             if constexpr (OUT == 1)
               out_row(b, lin)[c0 + cc] = __builtin_bit_cast(unsigned short, (veon_half_native)v);
             else
@@ -534,7 +570,9 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
           vs = vstart[seg_entry<DZ, DY, DX>(b, zo, yo, xo, g, Z, Y, X) + k];
         }
         const int vnext = __shfl_down(vs, 1);
-        const int n_occ = __popcll(__ballot(lane < NE && (lane % (GL + 1)) < GL && vnext > vs));
+        const unsigned long long occw = __ballot(lane < NE && (lane % (GL + 1)) < GL && vnext > vs);
+        const int n_occ = __popcll(occw);
+        [[maybe_unused]] const int fe = WIN ? first_empty_child<NSEG, GL>(occw, 0) : FULL;
         const RunTab rt = run_table<NSEG, GL>(vs, 0, lane);
         const int n = rl(rt.ce, NSEG - 1);
         for (int c0 = 0; c0 < c; c0 += 256) {
@@ -543,6 +581,7 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
           const int chl = chact ? ch : 0;
           float acc[4] = {0.f, 0.f, 0.f, 0.f};
           float m[4] = {kmin, kmin, kmin, kmin};
+          [[maybe_unused]] int wk[4] = {kNoWinner, kNoWinner, kNoWinner, kNoWinner};
           for (int base = 0; base < n; base += kWave) {
             const Stage1 st = stage1<NSEG, GL>(rt, vs, 0, base, n, lane);
             int rfj = 0;
@@ -556,8 +595,10 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
 #pragma unroll
               for (int k = 0; k < 4; ++k) acc[k] = fmaf(f[k], d, acc[k]);
               if ((st.last >> kk) & 1ull) {
+                [[maybe_unused]] const int child = WIN ? rl(st.slot, kk) : 0;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
+                  if constexpr (WIN) wk[k] = acc[k] > m[k] ? child : wk[k];
                   m[k] = vmax(m[k], acc[k]);
                   acc[k] = 0.f;
                 }
@@ -567,6 +608,14 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
           float v[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) v[k] = pooled_value(m[k], n_occ, FULL);
+          if constexpr (WIN) {
+            if (chact) {
+              unsigned pk = 0;
+#pragma unroll
+              for (int k = 0; k < 4; ++k) pk |= winner_code(m[k], wk[k], fe, FULL) << (8 * k);
+              *reinterpret_cast<unsigned*>(winner + (int64_t)pid * c + ch) = pk;
+            }
+          }
           if (chact) {
             if constexpr (OUT == 1) {
               *reinterpret_cast<uint2*>(out_row(b, lin) + ch) = pack_bf16x4(v);
@@ -633,6 +682,12 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
   unsigned noccp = 0;
 #pragma unroll
   for (int j = 0; j < kNP; ++j) noccp |= (unsigned)nocc[j] << (8 * j);
+  [[maybe_unused]] unsigned fep = 0;  // first empty child of the wave's pooled voxels
+  if constexpr (WIN) {
+#pragma unroll
+    for (int j = 0; j < kNP; ++j)
+      fep |= (unsigned)first_empty_child<NSEG, GL>(occm, NE * j) << (8 * j);
+  }
   // long lists belong to the workers: their runs become empty
   {
     const int first = __shfl(vs, NE * (jl < kNP ? jl : 0));
@@ -645,8 +700,12 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
     const int ch = c0 + lane * 4;
     const bool chact = ch < c;
     const int chl = chact ? ch : 0;  // idle lanes re-read channel 0 (never stored)
-    auto emit = [&](int j, float v0, float v1, float v2, float v3) {
+    auto emit = [&](int j, float v0, float v1, float v2, float v3, unsigned wpk) {
       const int xl = w + kMW * j;
+      if constexpr (WIN) {  // channels-last winner row: one coalesced store
+        if (chact)
+          *reinterpret_cast<unsigned*>(winner + ((int64_t)b * plane + lin0 + xl) * c + ch) = wpk;
+      }
       if constexpr (OUT == 1) {
         if (chact) {
           const float v[4] = {v0, v1, v2, v3};
@@ -667,6 +726,7 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
     };
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     float m[4] = {kmin, kmin, kmin, kmin};
+    [[maybe_unused]] int wk[4] = {kNoWinner, kNoWinner, kNoWinner, kNoWinner};
     for (int base = 0; base < n; base += kWave) {
       const Stage1 st = stage1<TSEG, GL>(rt, vs, 0, base, n, lane);
       int rfj = 0;
@@ -688,8 +748,10 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[k] = fmaf(f[k], d, acc[k]);
         if ((st.last >> kk) & 1ull) {
+          [[maybe_unused]] const int child = WIN ? rl(st.slot, kk) % FULL : 0;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
+            if constexpr (WIN) wk[k] = acc[k] > m[k] ? child : wk[k];
             m[k] = vmax(m[k], acc[k]);
             acc[k] = 0.f;
           }
@@ -697,10 +759,19 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
             const int jj = rl(pj, kk);
             const int no = (noccp >> (8 * jj)) & 0xff;  // (an indexed array would
                                                         // live in scratch)
-            emit(jj, pooled_value(m[0], no, FULL), pooled_value(m[1], no, FULL),
-                 pooled_value(m[2], no, FULL), pooled_value(m[3], no, FULL));
+            unsigned wpk = 0;
+            if constexpr (WIN) {
+              const int fe = (fep >> (8 * jj)) & 0xff;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) m[k] = kmin;
+              for (int k = 0; k < 4; ++k) wpk |= winner_code(m[k], wk[k], fe, FULL) << (8 * k);
+            }
+            emit(jj, pooled_value(m[0], no, FULL), pooled_value(m[1], no, FULL),
+                 pooled_value(m[2], no, FULL), pooled_value(m[3], no, FULL), wpk);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              m[k] = kmin;
+              if constexpr (WIN) wk[k] = kNoWinner;
+            }
           }
         }
       });
@@ -708,7 +779,7 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
     // pooled voxels without points: zeros
 #pragma unroll
     for (int j = 0; j < kNP; ++j)
-      if (mine[j] && nocc[j] == 0) emit(j, 0.f, 0.f, 0.f, 0.f);
+      if (mine[j] && nocc[j] == 0) emit(j, 0.f, 0.f, 0.f, 0.f, 0xffffffffu);
     if constexpr (OUT == 0) {
       if (lane < kNP) hotf[w + kMW * lane] = (skipm >> lane) & 1u;
       __syncthreads();
@@ -721,6 +792,121 @@ __global__ __launch_bounds__(kMW * 64) void k_rows_maxpool(
       }
       __syncthreads();
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// (A') backward of (A) with winners, for the lift's point layout.
+//
+// Every kept point of a lift has its own ranks_depth = ((img*D + d)*HW + hw) and
+// ranks_feat = img*HW + hw (view_transformer_raw.py:268-274): the points of a
+// feature pixel are its <= D depth bins.  pvox[ranks_depth] = voxel of that point
+// (-1: outside the grid) is therefore an inverted index that needs no sort.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_point_table(
+    const int* __restrict__ ranks_depth, const int* __restrict__ ranks_bev, int n_points,
+    const int* __restrict__ counts, int table_len, int n_voxels, int* __restrict__ pvox) {
+  if (counts != nullptr) n_points = counts[0] < n_points ? counts[0] : n_points;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_points) return;
+  const int rd = ranks_depth[i], v = ranks_bev[i];
+  if (rd >= 0 && rd < table_len && v >= 0 && v < n_voxels) pvox[rd] = v;
+}
+
+// One wave per feature pixel, lanes = 4 consecutive channels.  Lane i takes the
+// table entry of depth bin d0 + i; the bins with a voxel are compacted to lanes
+// 0..nv-1 in ascending d (so feat_grad is the fmaf chain in ascending d: one fixed
+// order, bit-reproducible), and the wave then walks them with wave-uniform row
+// addresses: pooled-gradient row (c floats) and winner row (c bytes) of the voxel's
+// pooled parent, kBwdRing points in flight.  No atomics: the wave owns feat_grad[pixel]
+// and the pixel's D entries of depth_grad (zero-filled by the caller: bins without a
+// voxel are not written).
+constexpr int kBwdWaves = 4, kBwdRing = 4;
+
+template <bool DG>
+__global__ __launch_bounds__(kBwdWaves * 64) void k_rows_maxpool_bwd(
+    const float* __restrict__ gout, const unsigned char* __restrict__ winner,
+    const int* __restrict__ pvox, const float* __restrict__ depth,
+    const float* __restrict__ feat, int c, int64_t n_pix, int D, int HW, int batch, int Z,
+    int Y, int X, float* __restrict__ depth_grad, float* __restrict__ feat_grad) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t pix = (int64_t)blockIdx.x * kBwdWaves + (threadIdx.x >> 6);  // wave-uniform
+  if (pix >= n_pix) return;
+  const int64_t img = pix / HW;
+  const int64_t dbase = img * D * HW + (pix - img * HW);
+  const int Yo = Y / 2, Xo = X / 2;
+  const int64_t n_vox = (int64_t)batch * Z * Y * X;
+  for (int c0 = 0; c0 < c; c0 += 256) {
+    const int ch = c0 + lane * 4;
+    const bool chact = ch < c;
+    const int chl = chact ? ch : 0;  // idle lanes re-read channel 0 (never stored)
+    float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (DG && chact) f = *reinterpret_cast<const float4*>(feat + pix * c + ch);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int d0 = 0; d0 < D; d0 += kWave) {
+      const int d = d0 + lane;
+      int pv = -1;
+      if (d < D) pv = pvox[dbase + (int64_t)d * HW];
+      const bool valid = pv >= 0 && pv < n_vox;
+      float dv = 0.f;
+      if (valid) dv = depth[dbase + (int64_t)d * HW];
+      const unsigned long long vm = __ballot(valid);
+      const int nv = __popcll(vm);
+      if (nv == 0) continue;
+      int q = 0, kc = 0;
+      if (valid) {
+        const int x = pv % X, y = (pv / X) % Y, zb = pv / (X * Y);  // zb = b*Z + z, Z even
+        q = ((zb >> 1) * Yo + (y >> 1)) * Xo + (x >> 1);
+        kc = ((zb & 1) * 2 + (y & 1)) * 2 + (x & 1);
+      }
+      // compaction: valid lane -> its rank among the valid ones, the others behind
+      const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(vm >> 32),
+                                                 __builtin_amdgcn_mbcnt_lo((unsigned)vm, 0));
+      const int dest = (valid ? rank : nv + lane - rank) * 4;
+      const int qs = __builtin_amdgcn_ds_permute(dest, q);
+      const int ks = __builtin_amdgcn_ds_permute(dest, kc | (lane << 8));
+      const float ds = __int_as_float(__builtin_amdgcn_ds_permute(dest, __float_as_int(dv)));
+      float dacc = 0.f;
+      for (int i = 0; i < nv; i += kBwdRing) {
+        float4 gr[kBwdRing];
+        unsigned wr[kBwdRing];
+#pragma unroll
+        for (int u = 0; u < kBwdRing; ++u) {  // unconditional: the tail re-reads the last row
+          const int ii = i + u < nv ? i + u : nv - 1;
+          const int64_t row = (int64_t)rl(qs, ii) * c + chl;
+          gr[u] = *reinterpret_cast<const float4*>(gout + row);
+          wr[u] = *reinterpret_cast<const unsigned*>(winner + row);
+        }
+#pragma unroll
+        for (int u = 0; u < kBwdRing; ++u) {
+          if (i + u < nv) {
+            const unsigned kk = (unsigned)rl(ks, i + u) & 0xffu;
+            const float dd = rlf(ds, i + u);
+            const float m0 = (wr[u] & 0xffu) == kk ? gr[u].x : 0.f;
+            const float m1 = ((wr[u] >> 8) & 0xffu) == kk ? gr[u].y : 0.f;
+            const float m2 = ((wr[u] >> 16) & 0xffu) == kk ? gr[u].z : 0.f;
+            const float m3 = (wr[u] >> 24) == kk ? gr[u].w : 0.f;
+            acc.x = fmaf(m0, dd, acc.x);
+            acc.y = fmaf(m1, dd, acc.y);
+            acc.z = fmaf(m2, dd, acc.z);
+            acc.w = fmaf(m3, dd, acc.w);
+            if constexpr (DG) {
+              float sdot = chact ? (m0 * f.x + m1 * f.y) + (m2 * f.z + m3 * f.w) : 0.f;
+#pragma unroll
+              for (int o = 32; o >= 1; o >>= 1) sdot += __shfl_xor(sdot, o);
+              if (lane == i + u) dacc = sdot;
+            }
+          }
+        }
+      }
+      if constexpr (DG) {
+        if (lane < nv) {
+          const int64_t e = dbase + (int64_t)(d0 + (ks >> 8)) * HW;
+          depth_grad[e] = c0 ? depth_grad[e] + dacc : dacc;
+        }
+      }
+    }
+    if (chact) *reinterpret_cast<float4*>(feat_grad + pix * c + ch) = acc;
   }
 }
 
@@ -1047,11 +1233,17 @@ int veon_bev_pool_v2_fwd_rows(int c, int batch, int64_t voxels_per_batch,
 
 int veon_bev_pool_rows_maxpool_chunk(void) { return kPV; }
 
-int veon_bev_pool_v2_fwd_rows_maxpool_ordered(
+}  // extern "C"
+
+namespace {
+
+// winner != NULL: the instantiation that also writes the winner volume (fp32 rows,
+// fp32 (B,C,Zo,Yo,Xo) output only)
+int rows_maxpool_launch(
     int c, int batch, int Z, int Y, int X, int dz, int dy, int dx, const float* depth,
     const void* feat, int feat_dtype, const int* ranks_depth, const int* ranks_feat,
     const int* vstart, void* out, int out_padded_bf16, int64_t feat_elems,
-    const int* chunk_order, void* stream) {
+    const int* chunk_order, uint8_t* winner, void* stream) {
   if (c <= 0 || (c & 3) || batch <= 0 || Z <= 0 || Y <= 0 || X <= 0 || !depth ||
       !feat || !vstart || !out)
     return VEON_ERR_BAD_ARG;
@@ -1076,6 +1268,16 @@ int veon_bev_pool_v2_fwd_rows_maxpool_ordered(
   const size_t lds_hot = (size_t)(2 * kCand + 4 + 2 * 8 + 8 * 256) * sizeof(int);
   const size_t lds_cold = (size_t)(256 * (kPV + 1) + kPV) * sizeof(float);
   const size_t lds_cf = lds_cold > lds_hot ? lds_cold : lds_hot;
+  if (winner != nullptr) {
+    if (feat_dtype != VEON_FEAT_F32 || out_padded_bf16 ||
+        (reinterpret_cast<uintptr_t>(winner) & 3u))
+      return VEON_ERR_BAD_ARG;
+    hipLaunchKernelGGL((k_rows_maxpool<VEON_FEAT_F32, 2, 2, 2, 0, true>), dim3((unsigned)wgs),
+                       dim3(kMW * 64), lds_cf, s, depth, feat, ranks_depth, ranks_feat, vstart,
+                       c, batch, Z, Y, X, out, g_pool_debug, kWorkers, kCold, kWarm,
+                       tile_order_lg(g_pool_debug, kOrderMp), chunk_order, winner);
+    return launch_status();
+  }
 #define VEON_ROWS_MP(FT)                                                            \
   do {                                                                              \
     if (out_padded_bf16)                                                            \
@@ -1083,18 +1285,90 @@ int veon_bev_pool_v2_fwd_rows_maxpool_ordered(
                          dim3(kMW * 64), lds_hot, s, depth, feat, ranks_depth,       \
                          ranks_feat, vstart, c, batch, Z, Y, X, out, g_pool_debug,  \
                          kWorkers, kCold, kWarm, tile_order_lg(g_pool_debug, kOrderMp), \
-                         chunk_order);                                              \
+                         chunk_order, nullptr);                                     \
     else                                                                            \
       hipLaunchKernelGGL((k_rows_maxpool<FT, 2, 2, 2, 0>), dim3((unsigned)wgs), \
                          dim3(kMW * 64), lds_cf, s, depth, feat, ranks_depth,        \
                          ranks_feat, vstart, c, batch, Z, Y, X, out, g_pool_debug,  \
                          kWorkers, kCold, kWarm, tile_order_lg(g_pool_debug, kOrderMp), \
-                         chunk_order);                                              \
+                         chunk_order, nullptr);                                     \
   } while (0)
   if (feat_dtype == VEON_FEAT_F32) VEON_ROWS_MP(VEON_FEAT_F32);
   else if (feat_dtype == VEON_FEAT_F16) VEON_ROWS_MP(VEON_FEAT_F16);
   else VEON_ROWS_MP(VEON_FEAT_BF16);
 #undef VEON_ROWS_MP
+  return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int veon_bev_pool_v2_fwd_rows_maxpool_ordered(
+    int c, int batch, int Z, int Y, int X, int dz, int dy, int dx, const float* depth,
+    const void* feat, int feat_dtype, const int* ranks_depth, const int* ranks_feat,
+    const int* vstart, void* out, int out_padded_bf16, int64_t feat_elems,
+    const int* chunk_order, void* stream) {
+  return rows_maxpool_launch(c, batch, Z, Y, X, dz, dy, dx, depth, feat, feat_dtype,
+                             ranks_depth, ranks_feat, vstart, out, out_padded_bf16,
+                             feat_elems, chunk_order, nullptr, stream);
+}
+
+int veon_bev_pool_v2_fwd_rows_maxpool_winner(
+    int c, int batch, int Z, int Y, int X, int dz, int dy, int dx, const float* depth,
+    const void* feat, int feat_dtype, const int* ranks_depth, const int* ranks_feat,
+    const int* vstart, void* out, int64_t feat_elems, const int* chunk_order,
+    uint8_t* winner, void* stream) {
+  if (!winner) return VEON_ERR_BAD_ARG;
+  return rows_maxpool_launch(c, batch, Z, Y, X, dz, dy, dx, depth, feat, feat_dtype,
+                             ranks_depth, ranks_feat, vstart, out, 0, feat_elems,
+                             chunk_order, winner, stream);
+}
+
+int veon_bev_pool_point_table(int n_points, int64_t table_len, int64_t n_voxels,
+                              const int* ranks_depth, const int* ranks_bev,
+                              const int* counts, int* pvox, void* stream) {
+  if (n_points < 0 || table_len <= 0 || table_len > 0x7fffffffLL || n_voxels <= 0 ||
+      n_voxels > 0x7fffffffLL || !pvox)
+    return VEON_ERR_BAD_ARG;
+  if (n_points > 0 && (!ranks_depth || !ranks_bev)) return VEON_ERR_BAD_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // -1 = the point lies outside the grid (all bytes 0xff)
+  if (hipMemsetAsync(pvox, 0xff, (size_t)table_len * sizeof(int), s) != hipSuccess)
+    return VEON_ERR_LAUNCH;
+  if (n_points > 0)
+    hipLaunchKernelGGL(k_point_table, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, s,
+                       ranks_depth, ranks_bev, n_points, counts, (int)table_len, (int)n_voxels,
+                       pvox);
+  return launch_status();
+}
+
+int veon_bev_pool_v2_bwd_rows_maxpool(int c, int n_images, int D, int HW, int batch, int Z,
+                                      int Y, int X, const float* pooled_grad,
+                                      const uint8_t* winner, const int* pvox,
+                                      const float* depth, const float* feat,
+                                      float* depth_grad, float* feat_grad, void* stream) {
+  if (c <= 0 || (c & 3) || n_images <= 0 || D <= 0 || HW <= 0 || batch <= 0 || Z <= 0 ||
+      Y <= 0 || X <= 0 || (Z & 1) || (Y & 1) || (X & 1) || !pooled_grad || !winner || !pvox ||
+      !depth || !feat || !feat_grad)
+    return VEON_ERR_BAD_ARG;
+  if ((int64_t)batch * Z * Y * X > 0x7ffffffeLL) return VEON_ERR_BAD_ARG;
+  if ((int64_t)n_images * D * HW > 0x7fffffffLL) return VEON_ERR_BAD_ARG;
+  if (!aligned16(pooled_grad) || !aligned16(feat) || !aligned16(feat_grad) ||
+      (reinterpret_cast<uintptr_t>(winner) & 3u))
+    return VEON_ERR_BAD_ARG;
+  const int64_t n_pix = (int64_t)n_images * HW;
+  const int64_t wgs = (n_pix + kBwdWaves - 1) / kBwdWaves;
+  if (wgs > 0x7fffffffLL) return VEON_ERR_BAD_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (depth_grad != nullptr)
+    hipLaunchKernelGGL((k_rows_maxpool_bwd<true>), dim3((unsigned)wgs), dim3(kBwdWaves * 64), 0,
+                       s, pooled_grad, winner, pvox, depth, feat, c, n_pix, D, HW, batch, Z, Y,
+                       X, depth_grad, feat_grad);
+  else
+    hipLaunchKernelGGL((k_rows_maxpool_bwd<false>), dim3((unsigned)wgs), dim3(kBwdWaves * 64), 0,
+                       s, pooled_grad, winner, pvox, depth, feat, c, n_pix, D, HW, batch, Z, Y,
+                       X, depth_grad, feat_grad);
   return launch_status();
 }
 

@@ -24,6 +24,28 @@ except Exception:
     _Base = nn.Module
 
 
+def block_max(volume, ds, first_max=False):
+    """The ``ds_feat`` block max of LSSViewTransformerRaw.forward
+    (view_transformer_raw.py:545-553): (B,C,Z,Y,X) -> (B,C,Z/dz,Y/dy,X/dx).  The
+    forward values are the same either way; the gradient differs where a block has
+    several maximal elements (the normal case: empty voxels are exact zeros and the
+    features come out of a ReLU):
+      first_max=False  ``amax`` over the three block axes: the gradient is split
+                       evenly over all maximal elements;
+      first_max=True   the reference's expression, ``torch.max(dim=-1).values`` over
+                       the block flattened in '(dz dh dw)' order: all of the gradient
+                       goes to the first maximal element.
+    Plain torch, any device."""
+    dz, dh, dw = (int(v) for v in ds)
+    b, c, z, h, w = volume.shape
+    blocks = volume.view(b, c, z // dz, dz, h // dh, dh, w // dw, dw)
+    if not first_max:
+        return blocks.amax(dim=(3, 5, 7))
+    flat = blocks.permute(0, 1, 2, 4, 6, 3, 5, 7).reshape(
+        b, c, z // dz, h // dh, w // dw, dz * dh * dw)
+    return torch.max(flat, dim=-1).values
+
+
 class LSSCore(_Base):
     """Geometry + index preparation + pooling; subclasses add the depth net."""
 
@@ -57,6 +79,12 @@ class LSSCore(_Base):
         # (veon_amd/placement.py: the same launch is ~15 % faster into a
         # well-placed allocation).
         self.persistent_output = False
+        # veon_amd extension (default off = amax under autograd, as before): train
+        # through the ds_feat max-pool with the reference's gradient (all of it to
+        # the first maximal element of a block, ``block_max``) and, where the fused
+        # kernels apply (ROCm, fp32 rows, ds_feat = (2,2,2), C % 4 == 0), without
+        # the un-pooled volume in either direction (bev_pool._LiftMaxpoolFused).
+        self.fuse_ds_grad = False
         self._out_buf = None
         self.placement_info = None
 
@@ -255,11 +283,15 @@ class LSSCore(_Base):
         self.__dict__.pop('_prepared', None)
 
     def _lift_maxpool(self, input, depth, feat, ds, out_volume=None):
-        """forward's pool + (dz,dy,dx) block max in one kernel (inference).
+        """forward's pool + (dz,dy,dx) block max in one kernel (inference, and
+        training with ``fuse_ds_grad``: the ranks of every prepare below have the
+        lift's layout, which is what ``lift_layout`` promises the op).
         depth (B,N,D,H,W), feat (B,N,C,H,W) -> (B,C,Z/dz,Y/dy,X/dx), or into
         ``out_volume`` (the Conv3d body's padded bf16 input)."""
         B = depth.shape[0]
         shape = self._bev_feat_shape(B, feat.shape[2])
+        lift = dict(lift_layout=(B * feat.shape[1], depth.shape[2], feat.shape[3],
+                                 feat.shape[4])) if torch.is_grad_enabled() else {}
         feat = feat.permute(0, 1, 3, 4, 2)
         if self.accelerate or not self.sync_free:
             self._drop_prepared()
@@ -268,7 +300,7 @@ class LSSCore(_Base):
             return _bp.bev_pool_v2_maxpool(
                 depth, feat, self.ranks_depth, self.ranks_feat, self.ranks_bev,
                 shape, self.interval_starts, self.interval_lengths, ds,
-                out_volume=out_volume)
+                out_volume=out_volume, **lift)
         sensor2ego, _, cam2imgs, post_rots, post_trans, bda = input[1:7]
         if self.sync_free:
             depth, extra = self._depth_table(depth)
@@ -286,7 +318,7 @@ class LSSCore(_Base):
             return _bp.bev_pool_v2_maxpool(
                 depth, feat, pre.ranks_depth, pre.ranks_feat, pre.ranks_bev,
                 shape, pre.interval_starts, pre.interval_lengths, ds,
-                counts=pre.counts, out_volume=out_volume, vstart=pre.vstart)
+                counts=pre.counts, out_volume=out_volume, vstart=pre.vstart, **lift)
         pri, comb, trans = _prep.camera_matrices(sensor2ego, cam2imgs, post_rots)
         ranks = _prep.prepare_from_matrices(
             self.frustum, pri, post_trans, comb, trans, bda,
@@ -295,7 +327,7 @@ class LSSCore(_Base):
             return None
         rb, rd, rf, st, ln = ranks
         return _bp.bev_pool_v2_maxpool(depth, feat, rd, rf, rb, shape, st, ln, ds,
-                                       out_volume=out_volume)
+                                       out_volume=out_volume, **lift)
 
     # ---------------------------------------------------------- entry points
     def pre_compute(self, input):

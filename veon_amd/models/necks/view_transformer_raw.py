@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from ..builder import register_neck
-from .lss_core import LSSCore
+from .lss_core import LSSCore, block_max
 from ... import depth_ops
 
 
@@ -109,9 +109,13 @@ class LSSViewTransformerRaw(LSSCore):
         return self.loss_depth_weight * loss
 
     def _can_fuse_ds(self, feat):
-        if not (self.use_ds and self.fuse_ds and feat.is_cuda
-                and not self.collapse_z and not torch.is_grad_enabled()):
+        if not (self.use_ds and self.fuse_ds and feat.is_cuda and not self.collapse_z):
             return False
+        if torch.is_grad_enabled() and not (
+                self.fuse_ds_grad and feat.dtype == torch.float32
+                and tuple(int(v) for v in self.ds) == (2, 2, 2) and feat.shape[2] % 4 == 0
+                and not getattr(self, 'sparse_depth_eps', None)):
+            return False   # training: only the differentiable fused form, opt-in
         x, y, z = (int(v) for v in self.grid_size)
         return z % self.ds[0] == 0 and y % self.ds[1] == 0 and x % self.ds[2] == 0
 
@@ -130,10 +134,14 @@ class LSSViewTransformerRaw(LSSCore):
         if windows and tuple(depth.shape) != (B, N, self.D, H, W):
             raise ValueError('two-hot windows of shape %r for a (%d,%d,%d,%d,%d) lift'
                              % (tuple(depth.shape), B, N, self.D, H, W))
-        if out_volume is not None and not self._can_fuse_ds(tran_feat):
+        if out_volume is not None and (torch.is_grad_enabled()
+                                       or not self._can_fuse_ds(tran_feat)):
             raise ValueError('out_volume needs the fused inference max-pool path '
                              '(ROCm tensors, no grad, ds_feat dividing the grid)')
         if self._can_fuse_ds(tran_feat):
+            if windows and torch.is_grad_enabled():
+                # the differentiable form has no compact path either: the dense tensor
+                depth, windows = depth.dense(thresholded=depth.eps > 0), False
             out = self._lift_maxpool(input,
                                      depth if windows else depth.view(B, N, self.D, H, W),
                                      tran_feat, self.ds, out_volume=out_volume)
@@ -152,8 +160,6 @@ class LSSViewTransformerRaw(LSSCore):
             depth = depth.view(B * N, depth.shape[2], H, W)
         bev_feat = self.view_transform(input, depth, tran_feat)
         if self.use_ds:
-            dz, dh, dw = self.ds
-            b, c, z, h, w = bev_feat.shape
-            bev_feat = bev_feat.view(b, c, z // dz, dz, h // dh, dh, w // dw, dw) \
-                .amax(dim=(3, 5, 7))
+            bev_feat = block_max(bev_feat, self.ds, first_max=self.fuse_ds_grad
+                                 and torch.is_grad_enabled())
         return bev_feat

@@ -308,20 +308,133 @@ def rows_maxpool(depth, feat, ranks_depth, ranks_feat, vstart, bev_feat_shape, d
         ret = torch.empty((B, C, Z // dz, Y // dy, X // dx), dtype=torch.float32,
                           device=dev)
         target, padded = ret, 0
-    if isinstance(chunk_order, str):
-        chunk_order = (cold_chunk_order(B, Z // dz, Y // dy, X // dx, dev)
-                       if COLD_ORDER == 'azimuth' else None)
-    if chunk_order is not None:
-        chunk = _lib.lib().veon_bev_pool_rows_maxpool_chunk()
-        want = B * (((Z // dz) * (Y // dy) * (X // dx) + chunk - 1) // chunk)
-        if (chunk_order.dtype != torch.int32 or chunk_order.numel() != want
-                or chunk_order.device != dev or not chunk_order.is_contiguous()):
-            raise _lib.VeonHipError('chunk_order must be a contiguous int32 permutation '
-                                    'of %d chunks on %s' % (want, dev))
+    chunk_order = _cold_order(chunk_order, B, Z // dz, Y // dy, X // dx, dev)
     _lib.launch('veon_bev_pool_v2_fwd_rows_maxpool_ordered', dev, C, B, Z, Y, X, dz, dy, dx,
                 depth, feat, _feat_code(feat), ranks_depth, ranks_feat, vstart, target,
                 padded, feat.numel(), chunk_order)
     return ret
+
+
+def _cold_order(chunk_order, B, Zo, Yo, Xo, dev):
+    """The ``chunk_order`` argument of the row max-pool entry points: 'default' = the
+    module's ``COLD_ORDER`` policy, None = the kernel's built-in order, or a checked
+    int32 permutation of the cold chunks."""
+    if isinstance(chunk_order, str):
+        chunk_order = (cold_chunk_order(B, Zo, Yo, Xo, dev)
+                       if COLD_ORDER == 'azimuth' else None)
+    if chunk_order is not None:
+        chunk = _lib.lib().veon_bev_pool_rows_maxpool_chunk()
+        want = B * ((Zo * Yo * Xo + chunk - 1) // chunk)
+        if (chunk_order.dtype != torch.int32 or chunk_order.numel() != want
+                or chunk_order.device != dev or not chunk_order.is_contiguous()):
+            raise _lib.VeonHipError('chunk_order must be a contiguous int32 permutation '
+                                    'of %d chunks on %s' % (want, dev))
+    return chunk_order
+
+
+def rows_maxpool_winner(depth, feat, ranks_depth, ranks_feat, vstart, bev_feat_shape,
+                        chunk_order='default'):
+    """``rows_maxpool`` for fp32 rows plus the winner volume of the block max
+    (include/veon_hip.h ``veon_bev_pool_v2_fwd_rows_maxpool_winner``):
+    -> ((B,C,Z/2,Y/2,X/2) fp32, (B,Z/2,Y/2,X/2,C) uint8)."""
+    B, Z, Y, X, C = [int(s) for s in bev_feat_shape]
+    dev = _lib.require_device(depth, feat, ranks_depth, ranks_feat, vstart)
+    if vstart.numel() != B * Z * Y * X + 1:
+        raise _lib.VeonHipError('voxel table does not match bev_feat_shape')
+    if feat.dtype != torch.float32:
+        raise _lib.VeonHipError('the max-pool with winners takes fp32 feature rows')
+    out = torch.empty((B, C, Z // 2, Y // 2, X // 2), dtype=torch.float32, device=dev)
+    winner = torch.empty((B, Z // 2, Y // 2, X // 2, C), dtype=torch.uint8, device=dev)
+    chunk_order = _cold_order(chunk_order, B, Z // 2, Y // 2, X // 2, dev)
+    _lib.launch('veon_bev_pool_v2_fwd_rows_maxpool_winner', dev, C, B, Z, Y, X, 2, 2, 2,
+                depth, feat, _lib.FEAT_F32, ranks_depth, ranks_feat, vstart, out,
+                feat.numel(), chunk_order, winner)
+    return out, winner
+
+
+def build_point_table(ranks_depth, ranks_bev, table_len, n_voxels, counts=None):
+    """Point -> voxel table of the fused backward (include/veon_hip.h
+    ``veon_bev_pool_point_table``): pvox[ranks_depth[p]] = ranks_bev[p], -1 where the
+    lift dropped the point.  ``counts``: device-side sizes of a sync-free prepare."""
+    dev = _lib.require_device(ranks_depth, ranks_bev, counts)
+    pvox = torch.empty(int(table_len), dtype=torch.int32, device=dev)
+    _lib.launch('veon_bev_pool_point_table', dev, ranks_bev.numel(), int(table_len),
+                int(n_voxels), ranks_depth, ranks_bev, counts, pvox)
+    return pvox
+
+
+def _point_table(ranks_depth, ranks_bev, interval_starts, table_len, n_voxels):
+    """The table cached beside the voxel table (on ``interval_starts``: it lives as
+    long as the cached ranks of accelerate=True do, one call otherwise)."""
+    key = (int(table_len), int(n_voxels), ranks_depth.data_ptr(), ranks_depth._version)
+    pvox = _cache_get(interval_starts, ranks_bev, '_veon_pvox', key)
+    if pvox is None:
+        pvox = build_point_table(ranks_depth, ranks_bev, table_len, n_voxels)
+        _cache_put(interval_starts, ranks_bev, '_veon_pvox', key, pvox)
+    return pvox
+
+
+class _LiftMaxpoolFused(torch.autograd.Function):
+    """Pool + (2,2,2) block max of a lift, differentiable w.r.t. depth and feat
+    without the un-pooled volume in either direction: forward = the row max-pool
+    kernel, which also records the winning child of every pooled (voxel, channel);
+    backward = one wave per feature pixel walking its depth bins through the
+    point -> voxel table.  The gradient is the reference's (bev_pool.py:43-83 behind
+    ``torch.max(dim=-1).values`` of view_transformer_raw.py:549-553): all of it to the
+    first maximal element of a block."""
+
+    @staticmethod
+    def forward(ctx, depth, feat, ranks_depth, ranks_feat, vstart, pvox, bev_feat_shape,
+                lift_layout):
+        out, winner = rows_maxpool_winner(depth, feat, ranks_depth, ranks_feat, vstart,
+                                          bev_feat_shape)
+        ctx.save_for_backward(depth, feat, winner, pvox)
+        ctx.geometry = (bev_feat_shape, lift_layout)
+        return out
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        depth, feat, winner, pvox = ctx.saved_tensors
+        (B, Z, Y, X, C), (n_images, D, H, W) = ctx.geometry
+        dev = _lib.require_device(out_grad, depth, feat)
+        og = out_grad.float().permute(0, 2, 3, 4, 1).contiguous()
+        depth_grad = torch.zeros_like(depth) if ctx.needs_input_grad[0] else None
+        feat_grad = torch.empty_like(feat)
+        _lib.launch('veon_bev_pool_v2_bwd_rows_maxpool', dev, C, n_images, D, H * W, B, Z, Y,
+                    X, og, winner, pvox, depth, feat, depth_grad, feat_grad)
+        return (depth_grad, feat_grad if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None, None)
+
+
+def _lift_maxpool_grad(depth, feat, ranks_depth, ranks_feat, ranks_bev, bev_feat_shape,
+                       interval_starts, ds, counts, vstart, lift_layout):
+    """The training form of ``bev_pool_v2_maxpool`` (its ``lift_layout`` argument)."""
+    B, Z, Y, X, C = [int(s) for s in bev_feat_shape]
+    n_images, D, H, W = [int(v) for v in lift_layout]
+    if (feat.dtype != torch.float32 or tuple(int(v) for v in ds) != (2, 2, 2) or C % 4
+            or Z % 2 or Y % 2 or X % 2 or feat.numel() >= 2 ** 31):
+        raise _lib.VeonHipError(
+            'the differentiable fused max-pool takes fp32 feature rows, ds = (2,2,2) '
+            'dividing the grid and C % 4 == 0 (got %s, ds %r, C %d)'
+            % (feat.dtype, tuple(ds), C))
+    if depth.numel() != n_images * D * H * W or feat.numel() != n_images * H * W * C:
+        raise _lib.VeonHipError('lift_layout %r does not match depth %r / feat %r'
+                                % (tuple(lift_layout), tuple(depth.shape),
+                                   tuple(feat.shape)))
+    _lib.require_device(depth, feat, ranks_depth, ranks_feat, ranks_bev, interval_starts)
+    n_vox = B * Z * Y * X
+    if counts is None:
+        if vstart is None:
+            vstart = _voxel_table(ranks_bev, interval_starts, B, Z * Y * X)
+        pvox = _point_table(ranks_depth, ranks_bev, interval_starts, depth.numel(), n_vox)
+    else:
+        if vstart is None:
+            vstart = build_voxel_table(ranks_bev, interval_starts, B, Z * Y * X,
+                                       attach=False, counts=counts)
+        pvox = build_point_table(ranks_depth, ranks_bev, depth.numel(), n_vox,
+                                 counts=counts)
+    return _LiftMaxpoolFused.apply(depth, feat, ranks_depth, ranks_feat, vstart, pvox,
+                                   (B, Z, Y, X, C), (n_images, D, H, W))
 
 
 def _rows_ok(C, ds=None, feat=None):
@@ -522,8 +635,8 @@ def build_row_table(ranks_bev, interval_starts, batch, voxels_per_batch,
 
 def bev_pool_v2_maxpool(depth, feat, ranks_depth, ranks_feat, ranks_bev,
                         bev_feat_shape, interval_starts, interval_lengths, ds,
-                        counts=None, out_volume=None, vstart=None):
-    """Inference-only fusion of ``bev_pool_v2`` with the (dz,dy,dx) block max of
+                        counts=None, out_volume=None, vstart=None, lift_layout=None):
+    """Fusion of ``bev_pool_v2`` with the (dz,dy,dx) block max of
     LSSViewTransformerRaw.forward (view_transformer_raw.py:545-553): returns
     (B, C, Z/dz, Y/dy, X/dx) without writing the full-resolution volume.
     Bit-equal to max-pooling ``bev_pool_v2``'s output.  Intervals must be
@@ -531,7 +644,26 @@ def bev_pool_v2_maxpool(depth, feat, ranks_depth, ranks_feat, ranks_bev,
     ``conv3d_ops.PaddedVolume`` of shape (B,C,Z/dz,Y/dy,X/dx)) receives the
     result rounded to bf16 in the Conv3d body's input layout instead, and is
     returned.  ``counts`` / ``vstart``: device-side sizes and dense voxel table of
-    a sync-free prepare (capacity-sized rank buffers)."""
+    a sync-free prepare (capacity-sized rank buffers).
+
+    Inference-only unless ``lift_layout = (n_images, D, H, W)`` is given: the caller's
+    promise that the ranks are those of a lift (ranks_depth = (img*D + d)*H*W + hw, one
+    point at most per value, ranks_feat = img*H*W + hw; view_transformer_raw.py:268-274
+    -- hand-made ranks do not have it, which is why it is not inferred).  Then, when
+    ``depth`` or ``feat`` needs a gradient, the call is differentiable
+    (``_LiftMaxpoolFused``: fp32 rows, ds = (2,2,2), C % 4 == 0, no ``out_volume``) with
+    the same forward values."""
+    if (lift_layout is not None and torch.is_grad_enabled()
+            and (depth.requires_grad or feat.requires_grad)):
+        if out_volume is not None:
+            raise ValueError('out_volume is the inference form of the fused max-pool: '
+                             'it cannot carry a gradient')
+        if feat.dtype != torch.float32:
+            raise _lib.VeonHipError('the differentiable fused max-pool takes fp32 '
+                                    'feature rows, got %s' % feat.dtype)
+        return _lift_maxpool_grad(depth.contiguous().float(), _rows(feat), ranks_depth,
+                                  ranks_feat, ranks_bev, bev_feat_shape, interval_starts,
+                                  ds, counts, vstart, lift_layout)
     depth = depth.contiguous().float()
     feat = _inference_feat(feat, depth)
     B, Z, Y, X, C = [int(s) for s in bev_feat_shape]
