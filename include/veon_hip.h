@@ -850,6 +850,45 @@ int veon_occ_retrieve(const void *feat, int feat_is_half, const int64_t *feat_st
                       int batch, const float *emb, int Q, float *emb_norms, float *score,
                       float *bin_prob, void *stream);
 
+/* ======== occ_align_loss.hip ======================================================== */
+
+/* The differentiable primitive of the 2D->3D feature-alignment loss (Proj2Dto3DLoss,
+ * models/semantic_net/loss/occ_loss_utils/occ3d_nuscenes.py:454-461, 497-504) from the
+ * LOW-resolution feature volume: the upsampled volume (san_in_veon_temporal.py:196-200)
+ * is formed in neither direction.  feat (B,C,zi,yi,xi) fp32 through five ELEMENT strides
+ * {b, c, z, y, x}; voxels: N int32 triples (x, y, z) in the grid (Zo,Yo,Xo), all of batch
+ * element `batch`, in any order, repeats allowed; labels: N int32 rows of table (K,C)
+ * fp32 contiguous; table_norms: K floats, written.  With f_i = trilinear
+ * (align_corners=False) upsample of feat at voxel i and t_i = table[labels_i]:
+ *   cos_out[i]     = f_i.t_i / (max(|f_i|, eps) * max(|t_i|, eps))
+ *   stats[2i]      = f_i.t_i / max(|t_i|, eps)        stats[2i+1] = |f_i|
+ * An entry whose voxel lies outside the grid or whose label lies outside [0, K) reads
+ * nothing and gets zeros (the caller refuses such entries beforehand).
+ * 1 <= C <= 1024, eps > 0.  No atomics: repeated calls are bit-identical. */
+int veon_occ_align_fwd(const float *feat, const int64_t *feat_strides, int C, int B, int zi,
+                       int yi, int xi, int Zo, int Yo, int Xo, const int *voxels,
+                       const int *labels, int N, int batch, const float *table, int K,
+                       float eps, float *table_norms, float *cos_out, float *stats,
+                       void *stream);
+/* Gradient of sum_i g[i] * cos_out[i] with respect to feat[batch], for the grid
+ * (2 zi, 2 yi, 2 xi) only, as autograd returns it for ATen's cosine_similarity:
+ *   d cos_i / d f_i = u_i / n_i - (f_i.u_i / n_i^2) * f_i / |f_i|,
+ *   n_i = max(|f_i|, eps), u_i = t_i / max(|t_i|, eps), the last factor 0 at f_i = 0.
+ * table_norms and stats as the forward wrote them.  The entries arrive grouped by
+ * output voxel: order (N) lists the entry indices voxel by voxel, seg_start (M + 1) the
+ * bounds of the M distinct voxels' runs in it, occ_rows (2zi * 2yi * 2xi, index
+ * (z * Yo + y) * Xo + x) the run of every output voxel or -1.  rows: workspace of M * C
+ * floats (one gradient row per distinct voxel).  grad: (zi, yi, xi, C) contiguous, every
+ * element stored exactly once (zeros where nothing arrives; no memset needed).  No
+ * atomics: the sums run in the order of `order` and of a fixed 64-candidate stencil, so
+ * repeated calls are bit-identical. */
+int veon_occ_align_bwd(const float *feat, const int64_t *feat_strides, int C, int B, int zi,
+                       int yi, int xi, const int *voxels, const int *labels, int N,
+                       int batch, const float *table, int K, float eps,
+                       const float *table_norms, const float *stats, const float *g,
+                       const int *order, const int *seg_start, int M, const int *occ_rows,
+                       float *rows, float *grad, void *stream);
+
 /* ======== memory.hip ================================================================ */
 
 /* Physically contiguous device memory (hipExtMallocWithFlags +

@@ -434,6 +434,31 @@ class VeonOccupancyPath(nn.Module):
         return retrieve_points(out['feat_low'], out['bin_low'], points_indices, embeddings,
                                self.occ_size, batch)
 
+    def occ_loss(self, out, voxel_semantics, mask_camera, img_inputs, sem_seg_ds,
+                 class_reflection, loss, prev_img_inputs=None):
+        """The training loss (``semantic_net.occ_loss.OccLossFB``, passed as ``loss``) of
+        the output of ``forward(..., return_features=True)``, read from the
+        LOW-resolution ``feat_low`` / ``bin_low``.  It needs a forward with grad enabled:
+        then these are the torch heads' tensors and the result can be back-propagated (the
+        no-grad native path's half ``PaddedVolume`` is refused); the upsampled feature
+        volume is formed in neither direction.  ``voxel_semantics`` / ``mask_camera``
+        (B, X, Y, Z) as Occ3D stores them; ``img_inputs``: the reference's 11-tuple
+        (images, sensor2egos, ego2globals, intrins, post_rots, post_trans, bda,
+        lidar2lidarego, lidarego2global, cam2camego, camego2global); ``sem_seg_ds``
+        (B, N, K2, h, w): the 2-D branch's class logits; ``class_reflection``: merged
+        class of each of its K2 classes.  ``prev_img_inputs`` is accepted and unused, as
+        in the reference.  -> dict of ``loss_binocc_c_0``, ``loss_featalign_det_c_0``,
+        ``loss_featalign_soft_c_0`` (the reference's rule for leaving a key out)."""
+        feat = out['feat_low']
+        if not isinstance(feat, torch.Tensor):
+            raise TypeError('occ_loss needs the torch heads\' feat_low (a forward with grad '
+                            'enabled); the no-grad native path returns a PaddedVolume')
+        results = dict(feat_occ=feat, bin_occ=out['bin_low'], occ_size=self.occ_size,
+                       sem_seg_ds=sem_seg_ds, class_reflection=class_reflection,
+                       ov_classifier_weight=self.ov_classifier_weight)
+        return loss(voxel_semantics, mask_camera, results, img_inputs,
+                    prev_img_inputs=prev_img_inputs)
+
     def forward(self, images, img_metas, prev_volumes=None, depth=None, with_2d=False,
                 return_features=False):
         """images (B, N, 3, H, W); img_metas = (sensor2egos, ego2globals, intrins,
