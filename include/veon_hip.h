@@ -812,6 +812,60 @@ int veon_warp_affine(const float *cur2glob, const float *prev2glob, int mat_stri
 int veon_volume_zero_halo_bf16(void *padded, int B, int C, int Z, int Y, int X,
                                void *stream);
 
+/* ======== conv3d_train.hip ========================================================== */
+
+/*
+ * ---- training of the Conv3d body on the padded grid (ResBlock3D with BN3d in training
+ * mode, align_net_occ3d.py:224-264, 363-399) ----
+ * All volumes are padded channels-last half grids as veon_conv3d_k3_bf16 takes and
+ * writes them, with the same guard rows, which must hold ZEROS here (they enter the
+ * weight gradient's contraction; a PaddedVolume allocates them zeroed and no kernel
+ * writes them).  The data gradient needs no entry point of its own: it is
+ * veon_conv3d_k3_bf16 on dy with the weight packed as [Cin][2-kz][2-ky][2-kx][Cout].
+ *
+ * Weight gradient: dw[co][kz][ky][kx][ci] (fp32) = sum over ALL padded rows of
+ * dy[row][co] * x[row + off(kz,ky,kx)][ci]; halo rows of dy are zero, so this is the
+ * sum over the interior.  MFMA with transposed LDS reads of both operands; the
+ * contraction is split over the rows, the partial results go to fp32 slabs in
+ * `workspace` (veon_conv3d_k3_wgrad_workspace_bytes, host-only; -1 for an unsupported
+ * shape) and are added in a fixed order: no atomics, bit-reproducible.
+ * Cin % 64 == 0 and Cout % 64 == 0, otherwise VEON_ERR_BAD_ARG; a workspace that is
+ * too small gives VEON_ERR_WORKSPACE.
+ */
+int64_t veon_conv3d_k3_wgrad_workspace_bytes(int B, int Z, int Y, int X, int Cin, int Cout);
+int veon_conv3d_k3_wgrad_bf16(const void *dy_padded, const void *x_padded, float *dw,
+                              void *workspace, int64_t workspace_bytes, int B, int Z,
+                              int Y, int X, int Cin, int Cout, void *stream);
+
+/*
+ * Train-mode BatchNorm3d on padded rows.  Per-channel sums over all padded rows in
+ * fp32, two stages, fixed order (halo rows are zero, so they are the interior's sums):
+ *   veon_bn3d_sums_bf16:     sums[0][c] = sum y,  sums[1][c] = sum y^2
+ *   veon_bn3d_bwd_sums_bf16: sums[0][c] = sum dz, sums[1][c] = sum dz * xhat, with
+ *                            dz = da * [a > 0], xhat = (y - mean[c]) * rstd[c]
+ * `workspace`: veon_bn3d_sums_workspace_bytes(C) bytes (host-only; -1: unsupported C).
+ *   veon_bn3d_apply_bf16:     out = y * scale[c] + shift[c] (+ ident) (ReLU if `relu`)
+ *   veon_bn3d_bwd_apply_bf16: dz as above, dy = ca[c] * dz + cb[c] * y + cc[c];
+ *                             dz_padded (optional) receives dz, the gradient of the
+ *                             identity branch
+ * on interior rows, ZERO on halo rows, rounded to half.  C % 8 == 0, C <= 2048.
+ * Outputs must not alias inputs.
+ */
+int64_t veon_bn3d_sums_workspace_bytes(int C);
+int veon_bn3d_sums_bf16(const void *y_padded, float *sums, void *workspace, int B, int C,
+                        int Z, int Y, int X, void *stream);
+int veon_bn3d_bwd_sums_bf16(const void *da_padded, const void *a_padded,
+                            const void *y_padded, const float *mean, const float *rstd,
+                            float *sums, void *workspace, int B, int C, int Z, int Y,
+                            int X, void *stream);
+int veon_bn3d_apply_bf16(const void *y_padded, const float *scale, const float *shift,
+                         const void *ident_padded, void *out_padded, int relu, int B,
+                         int C, int Z, int Y, int X, void *stream);
+int veon_bn3d_bwd_apply_bf16(const void *da_padded, const void *a_padded,
+                             const void *y_padded, const float *ca, const float *cb,
+                             const float *cc, void *dy_padded, void *dz_padded, int B,
+                             int C, int Z, int Y, int X, void *stream);
+
 /* ======== occ_head.hip ============================================================== */
 
 /* Tail of the occupancy path in one kernel (semantic_net/san_in_veon_temporal.py:

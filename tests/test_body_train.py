@@ -1,0 +1,153 @@
+"""Host-side checks of the native training path of the Conv3d body: the C ABI additions,
+the data gradient's weight packing, the closed-form train-mode BatchNorm backward the
+kernels implement, and the switch (plain torch, CPU)."""
+import copy
+import ctypes
+
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from veon_amd import _lib, conv3d_ops
+from veon_amd.models.semantic_net import ResBlock3D
+
+_I, _L, _P = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+
+# what the wrappers of veon_amd/conv3d_ops.py pass, stream last
+WANT = {
+    # B Z Y X Cin Cout (host-only)
+    'veon_conv3d_k3_wgrad_workspace_bytes': (_L, [_I] * 6),
+    # dy x dw workspace | workspace_bytes | B Z Y X Cin Cout | stream
+    'veon_conv3d_k3_wgrad_bf16': (_I, [_P] * 4 + [_L] + [_I] * 6 + [_P]),
+    'veon_bn3d_sums_workspace_bytes': (_L, [_I]),
+    # y sums workspace | B C Z Y X | stream
+    'veon_bn3d_sums_bf16': (_I, [_P] * 3 + [_I] * 5 + [_P]),
+    # da a y mean rstd sums workspace | B C Z Y X | stream
+    'veon_bn3d_bwd_sums_bf16': (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    # y scale shift ident out | relu B C Z Y X | stream
+    'veon_bn3d_apply_bf16': (_I, [_P] * 5 + [_I] * 6 + [_P]),
+    # da a y ca cb cc dy dz | B C Z Y X | stream
+    'veon_bn3d_bwd_apply_bf16': (_I, [_P] * 8 + [_I] * 5 + [_P]),
+}
+
+
+def test_header_and_libraries_carry_the_training_entry_points():
+    from veon_amd import build
+    build.build()
+    declared = set(_lib.declared_symbols())
+    for name, (restype, argtypes) in WANT.items():
+        assert name in declared, name
+        assert _lib._SIGNATURES[name] == (restype, argtypes), name
+    for flavour, path in _lib.LIB_PATHS.items():
+        lib = ctypes.CDLL(path)
+        for name in WANT:
+            assert hasattr(lib, name), (flavour, name)
+        lib.veon_abi_version.restype = ctypes.c_int
+        assert lib.veon_abi_version() == 2      # the additions are additive
+
+
+def test_workspace_size_is_slabs_of_the_weight_gradient():
+    """The host-only call returns what the wrapper allocates: split x Cout x 27 x Cin fp32,
+    with 9 x tiles x split workgroups within one round of the 256 CUs at the body's shape
+    (36 tiles of 128 x 128 x 3 taps -> 7 splits = 252); unsupported widths give -1."""
+    n = 256 * 27 * 256 * 4
+    assert conv3d_ops.wgrad_workspace_bytes(1, 8, 100, 100, 256, 256) == 7 * n
+    for shape in [(2, 4, 10, 12, 64, 64), (2, 3, 7, 5, 64, 128), (2, 3, 7, 5, 128, 64)]:
+        got = conv3d_ops.wgrad_workspace_bytes(*shape)
+        Cin, Cout = shape[4], shape[5]
+        slab = Cin * 27 * Cout * 4
+        t = 128 if Cin % 128 == 0 and Cout % 128 == 0 else 64
+        assert got > 0 and got % slab == 0
+        assert 9 * (Cout // t) * (Cin // t) * (got // slab) <= 256
+    assert conv3d_ops.wgrad_workspace_bytes(1, 2, 3, 3, 64, 72) == -1
+    assert conv3d_ops.wgrad_workspace_bytes(1, 2, 3, 3, 96, 64) == -1
+    assert conv3d_ops.wgrad_supported(256, 256) and not conv3d_ops.wgrad_supported(64, 72)
+    assert _lib.lib().veon_bn3d_sums_workspace_bytes(256) == 512 * 2 * 256 * 4
+    assert _lib.lib().veon_bn3d_sums_workspace_bytes(12) == -1
+
+
+def test_pack_weight_dgrad_gives_the_input_gradient():
+    """conv3d_k3's weight layout is [Cout'][kz][ky][kx][Cin']; read back as an
+    nn.Conv3d weight, pack_weight_dgrad(w) turns the forward conv into the input
+    gradient of F.conv3d(x, w, padding=1) (fp64, Cin != Cout)."""
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(2, 5, 3, 4, 6, generator=g, dtype=torch.float64, requires_grad=True)
+    w = torch.randn(7, 5, 3, 3, 3, generator=g, dtype=torch.float64)
+    gout = torch.randn(2, 7, 3, 4, 6, generator=g, dtype=torch.float64)
+    F.conv3d(x, w, padding=1).backward(gout)
+    wd = conv3d_ops.pack_weight_dgrad(w)
+    assert tuple(wd.shape) == (5, 3, 3, 3, 7) and wd.is_contiguous()
+    as_conv_weight = wd.permute(0, 4, 1, 2, 3)     # the inverse of pack_weight
+    got = F.conv3d(gout, as_conv_weight, padding=1)
+    assert ((got - x.grad).norm() / x.grad.norm()).item() <= 1e-12
+
+
+@pytest.mark.parametrize('identity', [False, True])
+@pytest.mark.parametrize('momentum', [0.1, None])
+def test_closed_form_bn_backward_equals_autograd(identity, momentum):
+    """bn_train_forward_ref / bn_train_backward_ref / bn_update_running (what the kernels
+    and the native function implement) against autograd through nn.BatchNorm3d
+    (+ identity) + ReLU in fp64, buffers included."""
+    g = torch.Generator().manual_seed(1)
+    C = 6
+    bn = nn.BatchNorm3d(C, momentum=momentum).double().train()
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5, generator=g)
+        bn.bias.normal_(0, 0.2, generator=g)
+        bn.running_mean.normal_(0, 0.2, generator=g)
+        bn.running_var.uniform_(0.5, 1.5, generator=g)
+    mine = copy.deepcopy(bn)
+    y = (torch.randn(2, C, 3, 4, 5, generator=g, dtype=torch.float64) * 1.5 + 0.3).requires_grad_(True)
+    ident = torch.randn(2, C, 3, 4, 5, generator=g, dtype=torch.float64).requires_grad_(True)
+    da = torch.randn(2, C, 3, 4, 5, generator=g, dtype=torch.float64)
+    for step in range(2):       # twice: num_batches_tracked drives momentum=None
+        for t in (y, ident, bn.weight, bn.bias):
+            t.grad = None
+        z = bn(y)
+        a = torch.relu(z + ident if identity else z)
+        a.backward(da)
+        a2, mean, var, rstd = conv3d_ops.bn_train_forward_ref(
+            y.detach(), mine.weight.detach(), mine.bias.detach(), mine.eps,
+            ident.detach() if identity else None)
+        conv3d_ops.bn_update_running(mine, mean, var, y.numel() // C)
+        dy, dgamma, dbeta, dz = conv3d_ops.bn_train_backward_ref(
+            da, a2, y.detach(), mean, rstd, mine.weight.detach())
+
+        def close(p, q):
+            return ((p - q).norm() / q.norm()).item() <= 1e-10
+        assert close(a2, a.detach()) and close(dy, y.grad)
+        assert close(dgamma, bn.weight.grad) and close(dbeta, bn.bias.grad)
+        if identity:
+            assert close(dz, ident.grad)
+        assert close(mine.running_mean, bn.running_mean)
+        assert close(mine.running_var, bn.running_var)
+        assert int(mine.num_batches_tracked) == int(bn.num_batches_tracked) == step + 1
+        # the affine form the backward kernel evaluates: dy = ca dz + cb y + cc
+        n = y.numel() // C
+        ca, cb, cc = conv3d_ops.bn_bwd_coefficients(torch.stack([dbeta, dgamma]), n,
+                                                    mine.weight.detach(), mean, rstd)
+        v = lambda t: t.double().view(1, -1, 1, 1, 1)     # noqa: E731
+        assert ((v(ca) * dz + v(cb) * y.detach() + v(cc) - dy).abs().max()
+                <= 1e-5 * dy.abs().max())    # fp32 coefficients
+
+
+def test_switch_is_off_by_default_and_cpu_keeps_the_torch_definition():
+    assert ResBlock3D.hip_train is False
+    torch.manual_seed(2)
+    blk = ResBlock3D(64, 64).train()
+    x = torch.randn(1, 64, 2, 3, 3)
+
+    def step(switch):
+        b = copy.deepcopy(blk)
+        xi = x.clone().requires_grad_(True)
+        ResBlock3D.hip_train = switch
+        try:
+            out = b(xi)
+            out.square().sum().backward()
+        finally:
+            ResBlock3D.hip_train = False
+        return [out.detach(), xi.grad] + [p.grad for p in b.parameters()] + \
+            [v for v in b.buffers()]
+    for p, q in zip(step(False), step(True)):
+        assert torch.equal(p, q)

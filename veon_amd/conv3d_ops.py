@@ -33,6 +33,21 @@ class PaddedVolume:
         B, C0, Z, Y, X = self.shape
         return PaddedVolume(B, C0 if C is None else C, Z, Y, X, self.device)
 
+    @classmethod
+    def from_storage(cls, storage, shape):
+        """The PaddedVolume of ``shape`` on an existing storage tensor (guard rows
+        included), e.g. one that autograd handed over."""
+        self = cls.__new__(cls)
+        self.shape = tuple(int(v) for v in shape)
+        B, C, Z, Y, X = self.shape
+        self.guard = int(_lib.lib().veon_conv3d_guard_rows(Y, X))
+        self.M = B * (Z + 2) * (Y + 2) * (X + 2)
+        assert tuple(storage.shape) == (self.M + 2 * self.guard, C)
+        assert storage.is_contiguous() and storage.dtype == _half.dtype()
+        self.storage = storage
+        self.rows = storage[self.guard:self.guard + self.M]
+        return self
+
     def interior(self):
         """(B,Z,Y,X,C) bf16 view of the un-padded voxels."""
         B, C, Z, Y, X = self.shape
@@ -87,6 +102,192 @@ def conv3d_k3(vol, w_packed, scale=None, shift=None, resid=None, relu=False,
                 None if resid is None else resid.rows, out.rows, B, Z, Y, X, Cin, Cout,
                 1 if relu else _ACT[act])
     return out
+
+
+# ------------------------------------------------- training of the Conv3d body
+def pack_weight_dgrad(w):
+    """nn.Conv3d weight (Cout,Cin,3,3,3) -> the packed weight [Cin][2-kz][2-ky][2-kx][Cout]
+    with which ``conv3d_k3`` of the output gradient is the INPUT gradient of the
+    stride-1 pad-1 convolution (taps flipped, channel roles swapped).  Plain torch, any
+    device; the dtype follows ``w`` (the caller rounds to the half type)."""
+    assert w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3)
+    return w.detach().flip(2, 3, 4).permute(1, 2, 3, 4, 0).contiguous()
+
+
+def _bshape(v, t):
+    return v.view(1, -1, *([1] * (t.dim() - 2)))
+
+
+def bn_train_forward_ref(y, gamma, beta, eps, ident=None, relu=True):
+    """Train-mode BatchNorm (+ identity, + ReLU) of ``y`` (B,C,...) in plain torch, the
+    mathematics the native passes implement: -> (a, mean, biased var, rstd)."""
+    dims = [0] + list(range(2, y.dim()))
+    mean = y.mean(dims)
+    var = y.var(dims, unbiased=False)
+    rstd = (var + eps).rsqrt()
+    z = (y - _bshape(mean, y)) * _bshape(rstd * gamma, y) + _bshape(beta, y)
+    if ident is not None:
+        z = z + ident
+    return (z.relu() if relu else z), mean, var, rstd
+
+
+def bn_train_backward_ref(da, a, y, mean, rstd, gamma, relu=True):
+    """The closed-form backward of ``bn_train_forward_ref``: -> (dy, dgamma, dbeta, dz);
+    dz is also the gradient of the identity branch."""
+    dims = [0] + list(range(2, y.dim()))
+    n = y.numel() // y.shape[1]
+    dz = da * (a > 0).to(da.dtype) if relu else da
+    xhat = (y - _bshape(mean, y)) * _bshape(rstd, y)
+    dbeta = dz.sum(dims)
+    dgamma = (dz * xhat).sum(dims)
+    dy = _bshape(gamma * rstd, y) * (dz - _bshape(dbeta, y) / n - xhat * _bshape(dgamma, y) / n)
+    return dy, dgamma, dbeta, dz
+
+
+def bn_update_running(bn, mean, var, n):
+    """What nn.BatchNorm3d does to its buffers in a training step, given the batch
+    mean and BIASED variance over ``n`` values per channel."""
+    if not bn.track_running_stats or bn.running_mean is None:
+        return
+    with torch.no_grad():
+        bn.num_batches_tracked += 1
+        f = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+        # n == 1 never gets here on the native path (nn.BatchNorm3d raises for one
+        # value per channel; the body's volumes have thousands)
+        unbiased = var * (float(n) / max(n - 1, 1))
+        bn.running_mean.mul_(1 - f).add_(mean.to(bn.running_mean.dtype), alpha=f)
+        bn.running_var.mul_(1 - f).add_(unbiased.to(bn.running_var.dtype), alpha=f)
+
+
+def bn_batch_stats(sums, n, eps):
+    """fp32 (2, C) sums of ``bn_sums`` -> (mean, biased var, rstd), the C-sized algebra in
+    fp64.  The variance is E[y^2] - mean^2 of fp32 SUMS: fp64 here adds no error of its
+    own but cannot recover what the sums lost, so var carries about 2^-24 (1 + mean^2 /
+    var) relative error times the sums' growth factor: fine for conv outputs (|mean| of the
+    order of std), not for a channel with |mean| >> std."""
+    s = sums.double()
+    mean = s[0] / n
+    var = (s[1] / n - mean * mean).clamp_min_(0)
+    return mean, var, (var + eps).rsqrt()
+
+
+def bn_bwd_coefficients(sums, n, gamma, mean, rstd):
+    """(dbeta, dgamma) sums + the forward's statistics -> the fp32 vectors (ca, cb, cc)
+    of ``bn_bwd_apply``: dy = ca dz + cb y + cc is the closed form
+    gamma rstd (dz - dbeta / n - xhat dgamma / n) with xhat = (y - mean) rstd."""
+    s = sums.double()
+    g, mu, r = gamma.double(), mean.double(), rstd.double()
+    ca = g * r
+    cb = -g * r * r * s[1] / n
+    cc = -g * r * s[0] / n - cb * mu
+    return ca.float().contiguous(), cb.float().contiguous(), cc.float().contiguous()
+
+
+# (kind, key..., device) -> tensor; reused: consumed inside one call.  As with the other
+# native caches, one buffer per shape and device serves every stream: two streams that
+# train the same shape concurrently must be ordered by the caller.
+_WORKSPACES = {}
+
+
+def _workspace(kind, nbytes, device, *key):
+    k = (kind,) + key + (str(device),)
+    ws = _WORKSPACES.get(k)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = torch.empty((int(nbytes) + 3) // 4, dtype=torch.float32, device=device)
+        _WORKSPACES[k] = ws
+    return ws
+
+
+def wgrad_workspace_bytes(B, Z, Y, X, Cin, Cout):
+    """Bytes of split-K slabs ``conv3d_k3_wgrad`` needs (host-only); -1: unsupported."""
+    return int(_lib.lib().veon_conv3d_k3_wgrad_workspace_bytes(B, Z, Y, X, Cin, Cout))
+
+
+def wgrad_supported(Cin, Cout):
+    return Cin % 64 == 0 and Cout % 64 == 0
+
+
+def conv3d_k3_wgrad(dy, x, out=None):
+    """Weight gradient of the 3x3x3 stride-1 pad-1 convolution on PaddedVolumes:
+    ``dy`` (Cout channels, halo zero), ``x`` (Cin) -> fp32 [Cout][3][3][3][Cin] (the
+    layout of ``pack_weight``).  Deterministic: split-K slabs added in a fixed order."""
+    dev = _lib.require_device(dy.storage, x.storage)
+    B, Cin, Z, Y, X = x.shape
+    Cout = dy.shape[1]
+    assert dy.shape == (B, Cout, Z, Y, X)
+    _lib.require_half(dy.rows, x.rows)
+    nbytes = wgrad_workspace_bytes(B, Z, Y, X, Cin, Cout)
+    if nbytes < 0:
+        raise _lib.VeonHipError('conv3d_k3_wgrad: unsupported shape %s -> %d channels'
+                                % (x.shape, Cout))
+    ws = _workspace('wgrad', nbytes, dev, B, Z, Y, X, Cin, Cout)
+    if out is None:
+        out = torch.empty((Cout, 3, 3, 3, Cin), dtype=torch.float32, device=dev)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == Cout * 27 * Cin
+    _lib.launch('veon_conv3d_k3_wgrad_bf16', dev, dy.rows, x.rows, out, ws, nbytes,
+                B, Z, Y, X, Cin, Cout)
+    return out
+
+
+def _bn_workspace(C, dev):
+    nbytes = int(_lib.lib().veon_bn3d_sums_workspace_bytes(C))
+    if nbytes < 0:
+        raise _lib.VeonHipError('train-mode BN: unsupported channel count %d' % C)
+    return _workspace('bn', nbytes, dev, C)
+
+
+def bn_sums(y):
+    """Per-channel (sum y, sum y^2) over the rows of a PaddedVolume (halo zero, so the
+    interior's sums) -> fp32 (2, C); two-stage, fixed order."""
+    dev = _lib.require_device(y.storage)
+    B, C, Z, Y, X = y.shape
+    sums = torch.empty((2, C), dtype=torch.float32, device=dev)
+    _lib.launch('veon_bn3d_sums_bf16', dev, y.rows, sums, _bn_workspace(C, dev),
+                B, C, Z, Y, X)
+    return sums
+
+
+def bn_apply(y, scale, shift, ident=None, relu=False, out=None):
+    """act(y * scale + shift (+ ident)) -> PaddedVolume, halo rows zero."""
+    dev = _lib.require_device(y.storage, scale, shift)
+    B, C, Z, Y, X = y.shape
+    assert scale.dtype == shift.dtype == torch.float32 and scale.numel() == shift.numel() == C
+    if out is None:
+        out = y.like()
+    assert out.shape == y.shape and out is not y and out is not ident
+    assert ident is None or ident.shape == y.shape
+    _lib.launch('veon_bn3d_apply_bf16', dev, y.rows, scale.contiguous(), shift.contiguous(),
+                None if ident is None else ident.rows, out.rows, 1 if relu else 0,
+                B, C, Z, Y, X)
+    return out
+
+
+def bn_bwd_sums(da, a, y, mean, rstd):
+    """Per-channel (sum dz, sum dz * xhat), dz = da * [a > 0], xhat = (y - mean) * rstd
+    -> fp32 (2, C): (dbeta, dgamma) of train-mode BN followed by ReLU."""
+    dev = _lib.require_device(da.storage, a.storage, y.storage, mean, rstd)
+    B, C, Z, Y, X = y.shape
+    assert da.shape == a.shape == y.shape
+    assert mean.dtype == rstd.dtype == torch.float32 and mean.numel() == rstd.numel() == C
+    sums = torch.empty((2, C), dtype=torch.float32, device=dev)
+    _lib.launch('veon_bn3d_bwd_sums_bf16', dev, da.rows, a.rows, y.rows, mean.contiguous(),
+                rstd.contiguous(), sums, _bn_workspace(C, dev), B, C, Z, Y, X)
+    return sums
+
+
+def bn_bwd_apply(da, a, y, ca, cb, cc, want_dz=False):
+    """dz = da * [a > 0]; dy = ca * dz + cb * y + cc on interior rows, zero halo ->
+    dy, or (dy, dz) with ``want_dz`` (the identity branch's gradient)."""
+    dev = _lib.require_device(da.storage, a.storage, y.storage, ca, cb, cc)
+    B, C, Z, Y, X = y.shape
+    assert da.shape == a.shape == y.shape
+    for v in (ca, cb, cc):
+        assert v.dtype == torch.float32 and v.numel() == C and v.is_contiguous()
+    dy = y.like()
+    dz = y.like() if want_dz else None
+    _lib.launch('veon_bn3d_bwd_apply_bf16', dev, da.rows, a.rows, y.rows, ca, cb, cc,
+                dy.rows, None if dz is None else dz.rows, B, C, Z, Y, X)
+    return (dy, dz) if want_dz else dy
 
 
 def deform_attention(kv, q, off, heads, samples=8, out=None):

@@ -1,0 +1,533 @@
+// Training of the 3x3x3 Conv3d body on the padded channels-last half grid of
+// conv3d.hip: the weight gradient on the matrix cores, and train-mode BatchNorm3d
+// (batch statistics) as bandwidth passes over the padded rows.
+//
+// One ConvModule3d in training mode (align_net_occ3d.py:363-399, BN3d with batch
+// statistics):
+//     y = conv(x, w)                       stored half, halo rows zero
+//     mu, var over the N interior voxels;  xhat = (y - mu) * rstd
+//     a = relu(gamma * xhat + beta (+ identity))         stored half, halo rows zero
+// and backwards, given da:
+//     dz = da * [a > 0];  dbeta = sum dz;  dgamma = sum dz * xhat
+//     dy = gamma * rstd * (dz - dbeta / N - xhat * dgamma / N)        halo rows zero
+//     dx = conv(dy, flip(w))    (veon_conv3d_k3_bf16 on a re-packed weight)
+//     dW[co][tap][ci] = sum_rows dy[row][co] * x[row + off(tap)][ci]
+//
+// Two facts of the padded layout carry all of it:
+//  * halo rows of y and dy are ZERO, so per-channel sums over ALL M padded rows are the
+//    sums over the interior; only the count N is the interior's.
+//  * a filter tap is the constant row offset off(tap) of conv3d.hip's header comment,
+//    so the weight gradient is 27 products dy^T . x_shifted contracted over all M
+//    padded rows; where row + off leaves the grid it reads guard rows, which are zero
+//    (and every product with a halo row of dy is zero anyway).
+// The apply passes write zero halo rows themselves (the shift beta would otherwise
+// leak into them): their output is the next conv's padded input.
+//
+// Weight gradient.  Both operands are stored [row][channel] and contracted over the
+// ROW index, so both MFMA fragments are transposed reads of a [row][channel] LDS image:
+// ds_read_b64_tr_b16 delivers, per 16-lane group, a 4-row x 16-column block with the
+// column on the lane.  Which four rows a lane group takes is free as long as both
+// operands take the same ones; here group g of a 16-row set takes rows
+// 8 (g & 1) + 4 (g >> 1) + 0..3, so that the two blocks of a 32-lane half lie 8 rows
+// apart (conflict-free on the swizzled 256-byte rows below).  One workgroup = one
+// (dz, dy) pair, a 128 x 128 (Cout x Cin) tile and ALL THREE dx taps: the taps read
+// rows k - 1, k, k + 1 of ONE x slab, and the dy fragments are reused three times.
+// The contraction is split over K; every split writes its fp32 partial tile to a slab
+// of the caller's workspace with plain stores, and a second kernel adds the slabs in
+// index order: no atomics, bit-reproducible.
+#include "mfma_common.h"
+
+namespace {
+
+typedef bf16x4 __attribute__((address_space(3))) lds_bf16x4;
+
+constexpr int WBK = 64;   // rows of the contraction per LDS slab
+
+// XOR key of the 16-byte chunks of an LDS row holding `chunks` (8 or 16) of them; for
+// 256-byte rows the image of the programming guide's transposed-read section.  Applied
+// on the DMA source address and again on the fragment read, per lane and per chunk.
+__device__ __forceinline__ int tr_key(int row, int chunks) {
+  return (((row & 3) << 2) | ((row >> 2) & 3)) & (chunks - 1);
+}
+
+// Cout tile = 32 TI, Cin tile = 32 TJ; 2 x 2 waves of (16 TI) x (16 TJ) x 3 taps each.
+template <int TI, int TJ>
+__global__ __launch_bounds__(256) void k_conv3d_wgrad(
+    const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, float* __restrict__ ws,
+    int Yp, int Xp, int Cin, int Cout, int nsteps, int steps_per_split, int nco, int nci) {
+  constexpr int CO_T = 32 * TI, CI_T = 32 * TJ;
+  constexpr int CHD = CO_T / 8, CHX = CI_T / 8;      // 16-byte chunks per LDS row
+  constexpr int RPD = 64 / CHD, RPX = 64 / CHX;      // rows per 1 KiB DMA piece
+  constexpr int DPIECES = WBK / RPD;
+  constexpr int XPIECES = (WBK + 2 + RPX - 1) / RPX;  // rows k0 - 1 .. k0 + 64
+  constexpr int D_ELEMS = WBK * CO_T, X_ELEMS = XPIECES * RPX * CI_T;
+  constexpr int BUF_ELEMS = D_ELEMS + X_ELEMS;
+  constexpr int DP = (DPIECES + 3) / 4, XP = (XPIECES + 3) / 4;
+  extern __shared__ __attribute__((aligned(16))) bf16_t smem[];   // [2][dy | x]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wco = wave >> 1, wci = wave & 1;
+  const int fr = lane & 15, fg = lane >> 4;
+
+  int t = blockIdx.x;
+  const int ci_t = t % nci; t /= nci;
+  const int co_t = t % nco;
+  const int zy = t / nco;                     // 3 (dz + 1) + (dy + 1)
+  const int split = blockIdx.y;
+  const int s0 = split * steps_per_split;
+  const int s1 = s0 + steps_per_split < nsteps ? s0 + steps_per_split : nsteps;
+
+  // LDS row j of the x slab of step s holds padded row 64 s + j + offrow; tap dx reads
+  // slab rows k + dx.  Rows outside [0, M) are guard rows (zeros).
+  const int offrow = ((zy / 3 - 1) * Yp + (zy % 3 - 1)) * Xp - 1;
+  const rsrc_t rsD = make_rsrc(dy + co_t * CO_T);
+  const rsrc_t rsX = make_rsrc(x + (int64_t)offrow * Cin + ci_t * CI_T);
+  int srcD[DP], srcX[XP];
+#pragma unroll
+  for (int j = 0; j < DP; ++j) {
+    const int r = (wave + 4 * j) * RPD + lane / CHD;
+    const int c = (lane % CHD) ^ tr_key(r, CHD);
+    srcD[j] = 2 * (r * Cout + c * 8);
+  }
+#pragma unroll
+  for (int j = 0; j < XP; ++j) {
+    const int r = (wave + 4 * j) * RPX + lane / CHX;
+    const int c = (lane % CHX) ^ tr_key(r, CHX);
+    srcX[j] = 2 * (r * Cin + c * 8);
+  }
+  auto dma = [&](int buf, int step) {
+    bf16_t* dD = smem + buf * BUF_ELEMS;
+    bf16_t* dX = dD + D_ELEMS;
+    const int k0 = step * WBK;
+#pragma unroll
+    for (int j = 0; j < DP; ++j)
+      if (wave + 4 * j < DPIECES)   // wave-uniform
+        buffer_load_lds16(rsD, (lptr_t)(dD + (wave + 4 * j) * 512), srcD[j],
+                          2 * k0 * Cout);
+#pragma unroll
+    for (int j = 0; j < XP; ++j)
+      if (wave + 4 * j < XPIECES)
+        buffer_load_lds16(rsX, (lptr_t)(dX + (wave + 4 * j) * 512), srcX[j],
+                          2 * k0 * Cin);
+  };
+
+  // transposed-read offsets (elements): lane 4q + p of a 16-lane group addresses row q,
+  // columns 4p .. 4p + 3 of its 4 x 16 block and receives column fr of the four rows
+  const int q = fr >> 2, p = fr & 3;
+  const int rbase = 8 * (fg & 1) + 4 * (fg >> 1) + q;   // + 16 per read, + 32 per k-step
+  int offD[TI], offX[3][TJ];
+#pragma unroll
+  for (int i = 0; i < TI; ++i) {
+    const int ch = wco * 2 * TI + 2 * i + (p >> 1);
+    offD[i] = rbase * CO_T + ((ch ^ tr_key(rbase, CHD)) * 8) + 4 * (p & 1);
+  }
+#pragma unroll
+  for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) {
+      const int ch = wci * 2 * TJ + 2 * j + (p >> 1);
+      // the key reads bits 0..3 of the row: unchanged by the + 16 / + 32 of the reads
+      offX[dx][j] = (rbase + dx) * CI_T + ((ch ^ tr_key(rbase + dx, CHX)) * 8) + 4 * (p & 1);
+    }
+
+  f32x4 acc[3][TI][TJ];
+#pragma unroll
+  for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) acc[dx][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  auto frag = [&](const bf16_t* base, int stride16) {
+    const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)base);
+    const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + stride16));
+    bf16x8 f;
+    f[0] = v0[0]; f[1] = v0[1]; f[2] = v0[2]; f[3] = v0[3];
+    f[4] = v1[0]; f[5] = v1[1]; f[6] = v1[2]; f[7] = v1[3];
+    return f;
+  };
+  auto compute = [&](int buf) {
+    const bf16_t* tD = smem + buf * BUF_ELEMS;
+    const bf16_t* tX = tD + D_ELEMS;
+#pragma unroll
+    for (int ks = 0; ks < WBK / 32; ++ks) {
+      bf16x8 fd[TI];
+#pragma unroll
+      for (int i = 0; i < TI; ++i)
+        fd[i] = frag(tD + offD[i] + ks * 32 * CO_T, 16 * CO_T);
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) {
+          const bf16x8 fx = frag(tX + offX[dx][j] + ks * 32 * CI_T, 16 * CI_T);
+#pragma unroll
+          for (int i = 0; i < TI; ++i)
+            // acc[dx][i][j][reg] = dW[co 16 i + 4 fg + reg][tap dx][ci 16 j + fr]
+            acc[dx][i][j] = mfma_16x16x32(fd[i], fx, acc[dx][i][j]);
+        }
+    }
+  };
+
+  if (s0 < s1) {   // workgroup-uniform; every lane stays active for the transposed reads
+    dma(0, s0);
+    __syncthreads();
+    for (int st = s0; st < s1; ++st) {
+      const int buf = (st - s0) & 1;
+      if (st + 1 < s1) dma(buf ^ 1, st + 1);
+      compute(buf);
+      __syncthreads();   // next slab landed (vmcnt drained) and this one released
+    }
+  }
+
+  // partial tile -> this split's slab [Cout][27][Cin], plain stores (64 B per 16 lanes)
+  float* slab = ws + (int64_t)split * Cout * 27 * Cin;
+#pragma unroll
+  for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+      for (int j = 0; j < TJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int co = co_t * CO_T + wco * 16 * TI + 16 * i + 4 * fg + r;
+          const int ci = ci_t * CI_T + wci * 16 * TJ + 16 * j + fr;
+          slab[((int64_t)co * 27 + zy * 3 + dx) * Cin + ci] = acc[dx][i][j][r];
+        }
+}
+
+// dW = slab 0 + slab 1 + ... in index order
+__global__ __launch_bounds__(256) void k_wgrad_reduce(const float4* __restrict__ ws,
+                                                      float4* __restrict__ dw, int64_t n4,
+                                                      int split) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  float4 s = ws[i];
+  for (int k = 1; k < split; ++k) {
+    const float4 v = ws[(int64_t)k * n4 + i];
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  dw[i] = s;
+}
+
+struct WgradPlan { int wide, nco, nci, nsteps, split, sps; };
+
+bool wgrad_plan(int B, int Z, int Y, int X, int Cin, int Cout, WgradPlan* pl) {
+  if (B <= 0 || Z <= 0 || Y <= 0 || X <= 0 || Cin <= 0 || Cout <= 0 || Cin % 64 != 0 ||
+      Cout % 64 != 0)
+    return false;
+  const int64_t M = (int64_t)B * (Z + 2) * (Y + 2) * (X + 2);
+  const int64_t cmax = Cin > Cout ? Cin : Cout;
+  // 32-bit byte offsets of the LDS DMA, as in conv3d.hip
+  if ((M + 2 * veon_conv3d_guard_rows(Y, X)) * cmax >= 0x3fffffffLL) return false;
+  pl->wide = (Cin % 128 == 0 && Cout % 128 == 0) ? 1 : 0;
+  const int tile = pl->wide ? 128 : 64;
+  pl->nco = Cout / tile;
+  pl->nci = Cin / tile;
+  pl->nsteps = (int)((M + WBK - 1) / WBK);
+  // Split over K: as many splits as keep 9 * tiles * split workgroups within ONE round of
+  // the 256 CUs (one workgroup per CU: 48 accumulator tiles per wave), but at least 8
+  // slabs of rows per split.  The body (256 -> 256, M = 104 040): 36 tiles x 7 = 252.
+  const int tiles = 9 * pl->nco * pl->nci;
+  int split = kNumCU / tiles;
+  if (split > pl->nsteps / 8) split = pl->nsteps / 8;
+  if (split < 1) split = 1;
+  pl->sps = (pl->nsteps + split - 1) / split;
+  pl->split = (pl->nsteps + pl->sps - 1) / pl->sps;   // no empty split
+  return true;
+}
+
+// ---------------------------------------------------------------- train-mode BatchNorm
+constexpr int kBnBlocks = 512;   // partial sums of stage one (upper bound)
+
+struct Half8 { float v[8]; };
+__device__ __forceinline__ Half8 load8(const bf16_t* p) {
+  const bf16x8 h = *reinterpret_cast<const bf16x8*>(p);
+  Half8 o;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o.v[k] = bf2f((bf16_t)h[k]);
+  return o;
+}
+__device__ __forceinline__ void store8(bf16_t* p, const float* v) {
+  const uint4 o = {pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]),
+                   pack_bf16(v[6], v[7])};
+  *reinterpret_cast<uint4*>(p) = o;
+}
+__device__ __forceinline__ bool row_interior(int64_t m, int Zp, int Yp, int Xp) {
+  const int YX = Yp * Xp;
+  const int pl = (int)(m / YX), rem = (int)(m - (int64_t)pl * YX);
+  const int y = rem / Xp, xx = rem - y * Xp, z = pl % Zp;
+  return z >= 1 && z <= Zp - 2 && y >= 1 && y <= Yp - 2 && xx >= 1 && xx <= Xp - 2;
+}
+
+// Stage one of the per-channel sums over all M padded rows (halo rows hold zeros, so
+// these ARE the interior's sums).  One lane = 8 channels of a row; a workgroup walks
+// its share of the rows, then adds its row-lanes in order and writes
+// part[block][2][C].  BWD = false: (sum y, sum y^2); BWD = true: (sum dz, sum dz xhat)
+// with dz = da [a > 0], xhat = (y - mean) rstd.
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_bn_sums(
+    const bf16_t* __restrict__ y, const bf16_t* __restrict__ da,
+    const bf16_t* __restrict__ a, const float* __restrict__ mean,
+    const float* __restrict__ rstd, float* __restrict__ part, int64_t M, int C,
+    int rows_per_block) {
+  __shared__ float red[256 * 16];
+  const int lpr = C / 8;                 // lanes per row
+  const int rpb = 256 / lpr;             // rows in flight
+  const int lr = threadIdx.x / lpr, lc = threadIdx.x % lpr;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < M ? r0 + rows_per_block : M;
+  float s1[8], s2[8], mu[8], rs[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { s1[k] = 0.f; s2[k] = 0.f; mu[k] = 0.f; rs[k] = 0.f; }
+  if (lr < rpb) {
+    if (BWD) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { mu[k] = mean[lc * 8 + k]; rs[k] = rstd[lc * 8 + k]; }
+    }
+    for (int64_t r = r0 + lr; r < r1; r += rpb) {
+      const Half8 vy = load8(y + r * C + lc * 8);
+      if (BWD) {
+        const Half8 vd = load8(da + r * C + lc * 8);
+        const Half8 va = load8(a + r * C + lc * 8);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const float dz = va.v[k] > 0.f ? vd.v[k] : 0.f;
+          s1[k] += dz;
+          s2[k] = fmaf(dz, (vy.v[k] - mu[k]) * rs[k], s2[k]);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          s1[k] += vy.v[k];
+          s2[k] = fmaf(vy.v[k], vy.v[k], s2[k]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    red[threadIdx.x * 16 + k] = s1[k];
+    red[threadIdx.x * 16 + 8 + k] = s2[k];
+  }
+  __syncthreads();
+  if (lr == 0) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      float s = red[lc * 16 + k];
+      for (int j = 1; j < rpb; ++j) s += red[(j * lpr + lc) * 16 + k];
+      part[((int64_t)blockIdx.x * 2 + (k >> 3)) * C + lc * 8 + (k & 7)] = s;
+    }
+  }
+}
+
+// Stage two: sums[2][C] = part[0] + part[1] + ... in block order
+__global__ __launch_bounds__(256) void k_bn_sums_final(const float* __restrict__ part,
+                                                       float* __restrict__ sums, int n,
+                                                       int nblocks) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float s = part[i];
+  for (int b = 1; b < nblocks; ++b) s += part[(int64_t)b * n + i];
+  sums[i] = s;
+}
+
+// out = act(y * scale + shift (+ identity)) on interior rows, zero on halo rows
+template <bool IDENT, bool RELU>
+__global__ __launch_bounds__(256) void k_bn_apply(
+    const bf16_t* __restrict__ y, const float* __restrict__ scale,
+    const float* __restrict__ shift, const bf16_t* __restrict__ ident,
+    bf16_t* __restrict__ out, int64_t M, int C, int Zp, int Yp, int Xp) {
+  const int lpr = C / 8;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t m = i / lpr;
+  const int c = (int)(i - m * lpr) * 8;
+  if (m >= M) return;
+  float v[8];
+  if (row_interior(m, Zp, Yp, Xp)) {
+    const Half8 vy = load8(y + m * C + c);
+    Half8 vi;
+    if (IDENT) vi = load8(ident + m * C + c);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      float t = fmaf(vy.v[k], scale[c + k], shift[c + k]);
+      if (IDENT) t += vi.v[k];
+      v[k] = RELU ? fmaxf(t, 0.f) : t;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = 0.f;
+  }
+  store8(out + m * C + c, v);
+}
+
+// dz = da [a > 0]; dy = ca dz + cb y + cc on interior rows (the closed form of the
+// train-mode BN backward with ca = gamma rstd, cb = -gamma rstd^2 dgamma / N,
+// cc = -gamma rstd dbeta / N - cb mean), zero on halo rows; dz_out (optional): the
+// gradient of the identity branch.
+__global__ __launch_bounds__(256) void k_bn_bwd_apply(
+    const bf16_t* __restrict__ da, const bf16_t* __restrict__ a,
+    const bf16_t* __restrict__ y, const float* __restrict__ ca,
+    const float* __restrict__ cb, const float* __restrict__ cc, bf16_t* __restrict__ dy,
+    bf16_t* __restrict__ dz_out, int64_t M, int C, int Zp, int Yp, int Xp) {
+  const int lpr = C / 8;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t m = i / lpr;
+  const int c = (int)(i - m * lpr) * 8;
+  if (m >= M) return;
+  float v[8], z[8];
+  if (row_interior(m, Zp, Yp, Xp)) {
+    const Half8 vd = load8(da + m * C + c);
+    const Half8 va = load8(a + m * C + c);
+    const Half8 vy = load8(y + m * C + c);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      z[k] = va.v[k] > 0.f ? vd.v[k] : 0.f;
+      v[k] = fmaf(ca[c + k], z[k], fmaf(cb[c + k], vy.v[k], cc[c + k]));
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { v[k] = 0.f; z[k] = 0.f; }
+  }
+  store8(dy + m * C + c, v);
+  if (dz_out != nullptr) store8(dz_out + m * C + c, z);
+}
+
+bool bn_shape_ok(int B, int C, int Z, int Y, int X) {
+  return B > 0 && C > 0 && Z > 0 && Y > 0 && X > 0 && C % 8 == 0 && C <= 2048 &&
+         (int64_t)B * (Z + 2) * (Y + 2) * (X + 2) <= 0x3fffffffLL;
+}
+
+int bn_sums_impl(bool bwd, const void* y, const void* da, const void* a, const float* mean,
+                 const float* rstd, float* sums, void* workspace, int B, int C, int Z,
+                 int Y, int X, void* stream) {
+  if (!bn_shape_ok(B, C, Z, Y, X) || !y || !sums || !workspace || !al16(y) ||
+      (bwd && (!da || !a || !mean || !rstd || !al16(da) || !al16(a))))
+    return VEON_ERR_BAD_ARG;
+  const int64_t M = (int64_t)B * (Z + 2) * (Y + 2) * (X + 2);
+  const int rpb = 256 / (C / 8);
+  // at least four rounds of rows per workgroup, at most kBnBlocks workgroups
+  int64_t rows = (M + kBnBlocks - 1) / kBnBlocks;
+  if (rows < 4 * rpb) rows = 4 * rpb;
+  const int nblocks = (int)((M + rows - 1) / rows);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  const bf16_t* py = static_cast<const bf16_t*>(y);
+  if (bwd)
+    hipLaunchKernelGGL(k_bn_sums<true>, dim3(nblocks), dim3(256), 0, s, py,
+                       static_cast<const bf16_t*>(da), static_cast<const bf16_t*>(a), mean,
+                       rstd, part, M, C, (int)rows);
+  else
+    hipLaunchKernelGGL(k_bn_sums<false>, dim3(nblocks), dim3(256), 0, s, py, nullptr,
+                       nullptr, nullptr, nullptr, part, M, C, (int)rows);
+  hipLaunchKernelGGL(k_bn_sums_final, dim3((2 * C + 255) / 256), dim3(256), 0, s, part,
+                     sums, 2 * C, nblocks);
+  return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t veon_conv3d_k3_wgrad_workspace_bytes(int B, int Z, int Y, int X, int Cin,
+                                             int Cout) {
+  WgradPlan pl;
+  if (!wgrad_plan(B, Z, Y, X, Cin, Cout, &pl)) return -1;
+  return (int64_t)pl.split * Cout * 27 * Cin * (int64_t)sizeof(float);
+}
+
+int veon_conv3d_k3_wgrad_bf16(const void* dy_padded, const void* x_padded, float* dw,
+                              void* workspace, int64_t workspace_bytes, int B, int Z,
+                              int Y, int X, int Cin, int Cout, void* stream) {
+  WgradPlan pl;
+  if (!wgrad_plan(B, Z, Y, X, Cin, Cout, &pl)) return VEON_ERR_BAD_ARG;
+  if (!dy_padded || !x_padded || !dw || !workspace || !al16(dy_padded) ||
+      !al16(x_padded) || !al16(dw) || !al16(workspace))
+    return VEON_ERR_BAD_ARG;
+  const int64_t n = (int64_t)Cout * 27 * Cin;
+  if (workspace_bytes < pl.split * n * (int64_t)sizeof(float)) return VEON_ERR_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bf16_t* D = static_cast<const bf16_t*>(dy_padded);
+  const bf16_t* Xv = static_cast<const bf16_t*>(x_padded);
+  float* ws = static_cast<float*>(workspace);
+  const dim3 grid((unsigned)(9 * pl.nco * pl.nci), (unsigned)pl.split);
+#define VEON_LAUNCH_WGRAD(TI, TJ)                                                       \
+  do {                                                                                  \
+    constexpr int chx = 32 * TJ / 8, rpx = 64 / chx;                                    \
+    constexpr int lds = 2 * (WBK * 32 * TI + (WBK + 2 + rpx - 1) / rpx * rpx * 32 * TJ) \
+                        * (int)sizeof(bf16_t);                                          \
+    static const hipError_t attr = hipFuncSetAttribute(                                 \
+        reinterpret_cast<const void*>(&k_conv3d_wgrad<TI, TJ>),                         \
+        hipFuncAttributeMaxDynamicSharedMemorySize, lds);                               \
+    if (attr != hipSuccess) return VEON_ERR_LAUNCH;                                     \
+    hipLaunchKernelGGL((k_conv3d_wgrad<TI, TJ>), grid, dim3(256), lds, s, D, Xv, ws,    \
+                       Y + 2, X + 2, Cin, Cout, pl.nsteps, pl.sps, pl.nco, pl.nci);     \
+  } while (0)
+  if (pl.wide) VEON_LAUNCH_WGRAD(4, 4); else VEON_LAUNCH_WGRAD(2, 2);
+#undef VEON_LAUNCH_WGRAD
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0,
+                     s, reinterpret_cast<const float4*>(ws), reinterpret_cast<float4*>(dw),
+                     n / 4, pl.split);
+  return launch_status();
+}
+
+int64_t veon_bn3d_sums_workspace_bytes(int C) {
+  if (C <= 0 || C % 8 != 0 || C > 2048) return -1;
+  return (int64_t)kBnBlocks * 2 * C * (int64_t)sizeof(float);
+}
+
+int veon_bn3d_sums_bf16(const void* y_padded, float* sums, void* workspace, int B, int C,
+                        int Z, int Y, int X, void* stream) {
+  return bn_sums_impl(false, y_padded, nullptr, nullptr, nullptr, nullptr, sums, workspace,
+                      B, C, Z, Y, X, stream);
+}
+
+int veon_bn3d_bwd_sums_bf16(const void* da_padded, const void* a_padded,
+                            const void* y_padded, const float* mean, const float* rstd,
+                            float* sums, void* workspace, int B, int C, int Z, int Y,
+                            int X, void* stream) {
+  return bn_sums_impl(true, y_padded, da_padded, a_padded, mean, rstd, sums, workspace, B,
+                      C, Z, Y, X, stream);
+}
+
+int veon_bn3d_apply_bf16(const void* y_padded, const float* scale, const float* shift,
+                         const void* ident_padded, void* out_padded, int relu, int B,
+                         int C, int Z, int Y, int X, void* stream) {
+  if (!bn_shape_ok(B, C, Z, Y, X) || !y_padded || !scale || !shift || !out_padded ||
+      !al16(y_padded) || !al16(out_padded) || (ident_padded && !al16(ident_padded)))
+    return VEON_ERR_BAD_ARG;
+  const int64_t M = (int64_t)B * (Z + 2) * (Y + 2) * (X + 2);
+  const int64_t n = M * (C / 8);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bf16_t* py = static_cast<const bf16_t*>(y_padded);
+  const bf16_t* pi = static_cast<const bf16_t*>(ident_padded);
+  bf16_t* po = static_cast<bf16_t*>(out_padded);
+#define VEON_BN_APPLY(ID, RL)                                                          \
+  hipLaunchKernelGGL((k_bn_apply<ID, RL>), grid, dim3(256), 0, s, py, scale, shift, pi, \
+                     po, M, C, Z + 2, Y + 2, X + 2)
+  if (pi) { if (relu) VEON_BN_APPLY(true, true); else VEON_BN_APPLY(true, false); }
+  else    { if (relu) VEON_BN_APPLY(false, true); else VEON_BN_APPLY(false, false); }
+#undef VEON_BN_APPLY
+  return launch_status();
+}
+
+int veon_bn3d_bwd_apply_bf16(const void* da_padded, const void* a_padded,
+                             const void* y_padded, const float* ca, const float* cb,
+                             const float* cc, void* dy_padded, void* dz_padded, int B,
+                             int C, int Z, int Y, int X, void* stream) {
+  if (!bn_shape_ok(B, C, Z, Y, X) || !da_padded || !a_padded || !y_padded || !ca || !cb ||
+      !cc || !dy_padded || !al16(da_padded) || !al16(a_padded) || !al16(y_padded) ||
+      !al16(dy_padded) || (dz_padded && !al16(dz_padded)))
+    return VEON_ERR_BAD_ARG;
+  const int64_t M = (int64_t)B * (Z + 2) * (Y + 2) * (X + 2);
+  const int64_t n = M * (C / 8);
+  hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream),
+                     static_cast<const bf16_t*>(da_padded),
+                     static_cast<const bf16_t*>(a_padded),
+                     static_cast<const bf16_t*>(y_padded), ca, cb, cc,
+                     static_cast<bf16_t*>(dy_padded), static_cast<bf16_t*>(dz_padded), M, C,
+                     Z + 2, Y + 2, X + 2);
+  return launch_status();
+}
+
+}  // extern "C"

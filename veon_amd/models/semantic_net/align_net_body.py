@@ -14,7 +14,10 @@ kernel (csrc/conv3d.hip): the lifted (B,C,Z,Y,X) fp32 volume is packed once into
 the zero-padded channels-last bf16 grid, every conv writes the next conv's
 padded input, BatchNorm (eval) + ReLU + the identity add are the conv's
 epilogue, and the result is unpacked once at the end.  Training and CPU tensors
-take the plain PyTorch formulation (the definition of the module).
+take the plain PyTorch formulation (the definition of the module), unless
+``ResBlock3D.hip_train`` is set: then a training-mode block on a ROCm volume trains
+on the same padded grid (csrc/conv3d_train.hip: train-mode BatchNorm passes, data
+gradient through the forward kernel, MFMA weight gradient).
 """
 import torch
 import torch.nn as nn
@@ -231,9 +234,140 @@ def semantic_inference_3d_fused(ov_classifier_weight, feat_occ, occ_size):
                                      align_corners=False)
 
 
+def _bn_train_native(y, bn):
+    """Batch statistics of the stored conv output ``y`` (PaddedVolume), the update of
+    ``bn``'s buffers, and the fp32 (scale, shift) of the apply pass."""
+    B, C, Z, Y, X = y.shape
+    n = B * Z * Y * X
+    mean, var, rstd = conv3d_ops.bn_batch_stats(conv3d_ops.bn_sums(y), n, bn.eps)
+    conv3d_ops.bn_update_running(bn, mean, var, n)
+    scale = bn.weight.detach().double() * rstd
+    shift = bn.bias.detach().double() - mean * scale
+    return mean.float(), rstd.float(), scale.float(), shift.float()
+
+
+class _ResBlockTrainFn(torch.autograd.Function):
+    """One training step of ``ResBlock3D`` on padded rows (csrc/conv3d_train.hip).  The
+    differentiable input and output are the STORAGE tensors of PaddedVolumes (half,
+    guard rows included), so consecutive blocks chain without leaving the layout; the
+    gradient between blocks is a padded half volume too.  Saved per conv: its input, its
+    stored output y, mean and rstd; the ReLU masks are read from the stored activations
+    (5 padded volumes per block: x, y1, a1, y2, out)."""
+
+    @staticmethod
+    def forward(ctx, xs, w1, g1, b1, w2, g2, b2, shape, blk):
+        half = _half.dtype()
+        x = conv3d_ops.PaddedVolume.from_storage(xs, shape)
+        # the half copies of the weights are re-packed from the fp32 parameters every step
+        y1 = conv3d_ops.conv3d_k3(x, conv3d_ops.pack_weight(w1))
+        mu1, r1, sc1, sh1 = _bn_train_native(y1, blk.conv1.bn)
+        a1 = conv3d_ops.bn_apply(y1, sc1, sh1, relu=True)
+        y2 = conv3d_ops.conv3d_k3(a1, conv3d_ops.pack_weight(w2))
+        mu2, r2, sc2, sh2 = _bn_train_native(y2, blk.conv2.bn)
+        out = conv3d_ops.bn_apply(y2, sc2, sh2, ident=x, relu=True)
+        ctx.shape = tuple(shape)
+        ctx.half = half
+        ctx.save_for_backward(xs, y1.storage, a1.storage, y2.storage, out.storage,
+                              mu1, r1, mu2, r2, w1, g1, w2, g2)
+        return out.storage
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        xs, y1s, a1s, y2s, outs, mu1, r1, mu2, r2, w1, g1, w2, g2 = ctx.saved_tensors
+        vol = lambda t: conv3d_ops.PaddedVolume.from_storage(t, ctx.shape)  # noqa: E731
+        x, y1, a1, y2, out = vol(xs), vol(y1s), vol(a1s), vol(y2s), vol(outs)
+        da = vol(dout.contiguous())
+        B, C, Z, Y, X = ctx.shape
+        n = B * Z * Y * X
+        need_x, need_w1, need_w2 = (ctx.needs_input_grad[i] for i in (0, 1, 4))
+        # conv2: BN + identity + ReLU backwards, then its two gradients; dz2 (the identity
+        # branch's gradient) is stored only when the block's input needs a gradient
+        s2 = conv3d_ops.bn_bwd_sums(da, out, y2, mu2, r2)
+        dy2 = conv3d_ops.bn_bwd_apply(
+            da, out, y2, *conv3d_ops.bn_bwd_coefficients(s2, n, g2, mu2, r2), want_dz=need_x)
+        dz2 = None
+        if need_x:
+            dy2, dz2 = dy2
+        dw2 = conv3d_ops.conv3d_k3_wgrad(dy2, a1) if need_w2 else None
+        da1 = conv3d_ops.conv3d_k3(dy2, conv3d_ops.pack_weight_dgrad(w2).to(ctx.half))
+        # conv1: BN + ReLU backwards
+        s1 = conv3d_ops.bn_bwd_sums(da1, a1, y1, mu1, r1)
+        dy1 = conv3d_ops.bn_bwd_apply(
+            da1, a1, y1, *conv3d_ops.bn_bwd_coefficients(s1, n, g1, mu1, r1))
+        dw1 = conv3d_ops.conv3d_k3_wgrad(dy1, x) if need_w1 else None
+        dxs = None
+        if need_x:
+            # dx = conv(dy1, flip(w1)) + dz2 (identity branch) as the conv's residual
+            dxs = conv3d_ops.conv3d_k3(dy1, conv3d_ops.pack_weight_dgrad(w1).to(ctx.half),
+                                       resid=dz2).storage
+
+        def wgrad(dw, w):    # [Cout][3][3][3][Cin] -> the parameter's layout and dtype
+            return None if dw is None else dw.permute(0, 4, 1, 2, 3).to(w.dtype)
+        return (dxs, wgrad(dw1, w1), s1[1].to(g1.dtype), s1[0].to(g1.dtype),
+                wgrad(dw2, w2), s2[1].to(g2.dtype), s2[0].to(g2.dtype), None, None)
+
+
+class _PackFn(torch.autograd.Function):
+    """(B,C,Z,Y,X) fp32 -> storage of its PaddedVolume; backwards the unpack."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.shape = tuple(x.shape)
+        return conv3d_ops.pack(x).storage
+
+    @staticmethod
+    def backward(ctx, g):
+        return conv3d_ops.unpack(conv3d_ops.PaddedVolume.from_storage(g.contiguous(),
+                                                                      ctx.shape))
+
+
+class _UnpackFn(torch.autograd.Function):
+    """storage of a PaddedVolume -> (B,C,Z,Y,X) fp32; backwards the pack."""
+
+    @staticmethod
+    def forward(ctx, xs, shape):
+        ctx.shape = tuple(shape)
+        return conv3d_ops.unpack(conv3d_ops.PaddedVolume.from_storage(xs, shape))
+
+    @staticmethod
+    def backward(ctx, g):
+        return conv3d_ops.pack(g).storage, None
+
+
+def run_blocks(blocks, x):
+    """``blocks`` (ResBlock3D) applied in order to the fp32 volume ``x``.  A run of
+    consecutive blocks that take the native training path (``ResBlock3D.hip_train``) is
+    packed once and unpacked once; every other block is called as it is."""
+    blocks = list(blocks)
+    i = 0
+    while i < len(blocks):
+        if not blocks[i]._hip_train_ok(x):
+            x = blocks[i](x)
+            i += 1
+            continue
+        shape = tuple(x.shape)
+        xs = _PackFn.apply(x)
+        while i < len(blocks) and blocks[i]._hip_train_ok(x):
+            xs = blocks[i]._train_native(xs, shape)
+            i += 1
+        x = _UnpackFn.apply(xs, shape)
+    return x
+
+
 class ResBlock3D(nn.Module):
     """relu(bn2(conv2(relu(bn1(conv1(x))))) + x) (align_net_occ3d.py:363-399;
-    ``stride`` / ``downsample`` as the reference, unused by VEON)."""
+    ``stride`` / ``downsample`` as the reference, unused by VEON).
+
+    ``hip_train`` (class attribute, default False): opt-in native TRAINING path.  When
+    set, a training-mode block on a ROCm fp32 tensor whose widths the kernels support
+    runs ``_ResBlockTrainFn`` (train-mode BatchNorm with batch statistics, MFMA convs,
+    data and weight gradients in HIP); anything else takes the torch definition.
+    As on the inference fast path, the native path does not go through the
+    ``__call__`` of ``conv1`` / ``conv2`` (nor, inside a run of ``run_blocks``, of the
+    block): forward and backward hooks registered on them do not fire."""
+
+    hip_train = False
 
     def __init__(self, channels_in, channels_out, stride=1, downsample=None,
                  use_checkpoint=False):
@@ -247,9 +381,30 @@ class ResBlock3D(nn.Module):
         self.use_checkpoint = use_checkpoint
 
     def forward(self, x):
+        if self._hip_train_ok(x):
+            return run_blocks([self], x)
         identity = x if self.downsample is None else self.downsample(x)
         x = self.conv2(self.conv1(x))
         return self.relu(x + identity)
+
+    def _hip_train_ok(self, x):
+        """The native training path's own test: the switch, training mode, a ROCm fp32
+        volume, the inference path's structure test and the weight gradient's widths
+        (both multiples of 64: stricter than ``hip_supported``), BN with buffers."""
+        if not (self.hip_train and self.training and torch.is_tensor(x) and x.is_cuda
+                and x.dtype == torch.float32 and x.dim() == 5 and self.hip_supported()):
+            return False
+        c1, c2 = self.conv1, self.conv2
+        return (conv3d_ops.wgrad_supported(c1.conv.in_channels, c1.conv.out_channels)
+                and conv3d_ops.wgrad_supported(c2.conv.in_channels, c2.conv.out_channels)
+                and all(cm.bn is not None and cm.bn.training and cm.bn.affine
+                        and cm.bn.track_running_stats and cm.conv.bias is None
+                        and cm.conv.weight.dtype == torch.float32 for cm in (c1, c2)))
+
+    def _train_native(self, xs, shape):
+        c1, c2 = self.conv1, self.conv2
+        return _ResBlockTrainFn.apply(xs, c1.conv.weight, c1.bn.weight, c1.bn.bias,
+                                      c2.conv.weight, c2.bn.weight, c2.bn.bias, shape, self)
 
     def hip_supported(self):
         c1, c2 = self.conv1.conv, self.conv2.conv
@@ -308,9 +463,9 @@ class AlignBody3D(nn.Module):
                                 and all(b.hip_supported() for b in blocks)):
             x, from_volume = conv3d_ops.unpack(x), False
         if not from_volume and not self._use_hip(x):
-            for blk in blocks:
-                x = blk(x)
-            return x
+            # torch definition, or (ResBlock3D.hip_train) the native training path with
+            # one pack and one unpack around each run of native blocks
+            return run_blocks(blocks, x)
         if self._hip is None:
             self._hip = [(b.conv1.folded(), b.conv2.folded())
                          for b in self.layers_3d_body]

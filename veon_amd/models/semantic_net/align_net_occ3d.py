@@ -24,7 +24,8 @@ import torch
 import torch.nn as nn
 
 from ... import conv3d_ops
-from .align_net_body import AlignBody3D, PredHead3DOcc, PredHead3DSem, ResBlock3D
+from .align_net_body import (AlignBody3D, PredHead3DOcc, PredHead3DSem, ResBlock3D,
+                              run_blocks)
 from .fusion_layers import build_fusion_layer_lift
 from .temporal_fusion import TemporalFusionMultiFrame
 
@@ -177,12 +178,21 @@ class AlignNetOcc3D(nn.Module):
                 x = self.__dict__['_body'](x, return_volume=True)
                 return {'bin_occ': self.occupancy_pred(x), 'feat_occ': self.feat_pred(x)}
         x = None
-        for idx, layer_3d in enumerate(self.layers_3d_body):
+        blocks = list(self.layers_3d_body)
+        idx = 0
+        while idx < len(blocks):
             x = self.fuse(idx, x, clip_features, supp_features, depth, img_metas,
                           (h, w), (H, W))
             if idx == self.tf_layers and occ_feat_prevs is not None:
                 x = self._temporal(x, occ_feat_prevs)
-            x = layer_3d(x)
+            # the blocks up to the next fusion / temporal step form one run (the native
+            # training path packs once per run; the torch path calls them one by one)
+            stop = idx + 1
+            while stop < len(blocks) and stop not in self.fusion_map and not (
+                    stop == self.tf_layers and occ_feat_prevs is not None):
+                stop += 1
+            x = run_blocks(blocks[idx:stop], x)
+            idx = stop
         return {'bin_occ': self.occupancy_pred(x), 'feat_occ': self.feat_pred(x)}
 
     def _temporal(self, x, prevs):
