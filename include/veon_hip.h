@@ -866,6 +866,59 @@ int veon_bn3d_bwd_apply_bf16(const void *da_padded, const void *a_padded,
                              const float *cc, void *dy_padded, void *dz_padded, int B,
                              int C, int Z, int Y, int X, void *stream);
 
+/* ======== conv2d_train.hip ========================================================== */
+
+/*
+ * ---- training of the HSA ConvBlock on padded images (conv3x3 + bias -> GELU -> LN ->
+ * conv3x3 + bias -> LN, highres_side_adaptor.py:31-52) ----
+ * All images are padded channels-last half grids [B][Y+2][X+2][C] as veon_conv2d_k3_bf16
+ * takes and writes them, with veon_conv3d_guard_rows(Y, X) guard rows before and after.
+ * The GUARD ROWS OF x MUST HOLD ZEROS for the weight gradient (they enter its
+ * contraction; a PaddedImage allocates them zeroed and no kernel writes them).  The data
+ * gradient needs no entry point of its own: it is veon_conv2d_k3_bf16 on dy with the
+ * weight packed as [Cin][2-ky][2-kx][Cout].
+ *
+ * Weight gradient: dw[co][ky][kx][ci] (fp32) = sum over ALL padded rows of
+ * dy[row][co] * x[row + (ky-1)(X+2) + (kx-1)][ci]; halo rows of dy are zero, so this is
+ * the sum over the interior.  The kernel of veon_conv3d_k3_wgrad_bf16 with one ky per
+ * workgroup; split over the rows into fp32 slabs of `workspace`
+ * (veon_conv2d_k3_wgrad_workspace_bytes, host-only; -1 for an unsupported shape), added
+ * in index order: no atomics, bit-reproducible.  Cin % 64 == 0 and Cout % 64 == 0,
+ * otherwise VEON_ERR_BAD_ARG; a workspace that is too small gives VEON_ERR_WORKSPACE.
+ */
+int64_t veon_conv2d_k3_wgrad_workspace_bytes(int B, int Y, int X, int Cin, int Cout);
+int veon_conv2d_k3_wgrad_bf16(const void *dy_padded, const void *x_padded, float *dw,
+                              void *workspace, int64_t workspace_bytes, int B, int Y,
+                              int X, int Cin, int Cout, void *stream);
+
+/*
+ * out = LayerNorm(GELU(in)) over the channels of every pixel: GELU in its erf form in
+ * fp32 from the stored half value, statistics in fp32, halo rows written as ZEROS (the
+ * next conv's padded input).  C % 8 == 0, C <= 1024, as veon_image_layernorm_bf16.
+ */
+int veon_image_gelu_layernorm_bf16(const void *in_padded, const float *gamma,
+                                   const float *beta, void *out_padded, int B, int C,
+                                   int Y, int X, float eps, void *stream);
+
+/*
+ * Backward of that LayerNorm in one pass over the rows; the row statistics are
+ * recomputed from the LayerNorm's stored input x_padded (`gelu_in` != 0: the
+ * LayerNorm's input was GELU(x), and dx is the gradient of x, through GELU' too).
+ * `dout`: a padded half image (dout_tokens_f32 == 0) or compact fp32 tokens
+ * (B, Y*X, C).  dx_padded: padded half image, halo rows written as ZEROS.
+ * sums[3][C] (fp32) over the interior rows: [0] dgamma = sum dout * xhat,
+ * [1] dbeta = sum dout, [2] sum dx (the gradient of the bias of the conv in front; fp32
+ * values, before dx is rounded to half).  Two stages in a fixed order, no atomics;
+ * `workspace`: veon_image_layernorm_bwd_workspace_bytes(C) bytes (host-only; -1:
+ * unsupported C).  C % 8 == 0, C <= 1024.  Outputs must not alias inputs.
+ */
+int64_t veon_image_layernorm_bwd_workspace_bytes(int C);
+int veon_image_layernorm_bwd_bf16(const void *dout, int dout_tokens_f32,
+                                  const void *x_padded, int gelu_in, const float *gamma,
+                                  void *dx_padded, float *sums, void *workspace,
+                                  int64_t workspace_bytes, int B, int C, int Y, int X,
+                                  float eps, void *stream);
+
 /* ======== occ_head.hip ============================================================== */
 
 /* Tail of the occupancy path in one kernel (semantic_net/san_in_veon_temporal.py:

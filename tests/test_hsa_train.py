@@ -1,0 +1,142 @@
+"""Host-side checks of the native training path of the HSA ConvBlocks: the C ABI additions,
+the 2-D weight gradient's workspace plan, the data gradient's weight packing, the
+closed-form LayerNorm (+ GELU) backward the kernels implement, and the switch (plain
+torch, CPU)."""
+import copy
+import ctypes
+
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from veon_amd import _lib, conv3d_ops
+from veon_amd.models.semantic_net.hsa_network import ConvBlock
+
+_I, _L, _P, _F = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float
+
+# what the wrappers of veon_amd/conv3d_ops.py pass, stream last
+WANT = {
+    # B Y X Cin Cout (host-only)
+    'veon_conv2d_k3_wgrad_workspace_bytes': (_L, [_I] * 5),
+    # dy x dw workspace | workspace_bytes | B Y X Cin Cout | stream
+    'veon_conv2d_k3_wgrad_bf16': (_I, [_P] * 4 + [_L] + [_I] * 5 + [_P]),
+    # in gamma beta out | B C Y X | eps | stream
+    'veon_image_gelu_layernorm_bf16': (_I, [_P] * 4 + [_I] * 4 + [_F] + [_P]),
+    'veon_image_layernorm_bwd_workspace_bytes': (_L, [_I]),
+    # dout | tokens | x | gelu_in | gamma dx sums workspace | bytes | B C Y X | eps | stream
+    'veon_image_layernorm_bwd_bf16': (_I, [_P, _I, _P, _I] + [_P] * 4 + [_L] + [_I] * 4
+                                      + [_F] + [_P]),
+}
+
+
+def test_header_and_libraries_carry_the_hsa_training_entry_points():
+    from veon_amd import build
+    build.build()
+    declared = set(_lib.declared_symbols())
+    for name, (restype, argtypes) in WANT.items():
+        assert name in declared, name
+        assert _lib._SIGNATURES[name] == (restype, argtypes), name
+    for flavour, path in _lib.LIB_PATHS.items():
+        lib = ctypes.CDLL(path)
+        for name in WANT:
+            assert hasattr(lib, name), (flavour, name)
+        lib.veon_abi_version.restype = ctypes.c_int
+        assert lib.veon_abi_version() == 2      # the additions are additive
+
+
+def test_workspace_size_is_slabs_of_the_2d_weight_gradient():
+    """split x Cout x 9 x Cin fp32.  The ConvBlock's shape (384 -> 384 on 6 x 64 x 176,
+    M = 70 488 padded rows, 1102 slabs of 64): 27 workgroups of 128 x 128 x 3 taps per
+    split, 256 // 27 = 9 splits = 243 workgroups.  (2, 64, 64, 10, 12): 336 rows are six
+    slabs, fewer than the eight a split must have, so one split."""
+    assert conv3d_ops.wgrad2d_workspace_bytes(6, 64, 176, 384, 384) == 9 * 384 * 9 * 384 * 4
+    assert conv3d_ops.wgrad2d_workspace_bytes(2, 10, 12, 64, 64) == 1 * 64 * 9 * 64 * 4
+    assert conv3d_ops.wgrad2d_workspace_bytes(1, 3, 3, 64, 72) == -1
+    assert conv3d_ops.wgrad2d_workspace_bytes(1, 3, 3, 96, 64) == -1
+    lib = _lib.lib()
+    assert lib.veon_image_layernorm_bwd_workspace_bytes(384) % (3 * 384 * 4) == 0
+    assert lib.veon_image_layernorm_bwd_workspace_bytes(12) == -1
+    assert lib.veon_image_layernorm_bwd_workspace_bytes(1032) == -1
+
+
+def _padded_row_conv(x, wp):
+    """conv2d_k3's definition in plain torch: x (B,Cin,Y,X), wp [Cout][ky][kx][Cin] ->
+    out[row][co] = sum_taps x_rows[row + (ky-1)(X+2) + (kx-1)] . wp[co][ky][kx] on the
+    zero-padded rows (guard rows zero), interior rows kept."""
+    B, Cin, Y, X = x.shape
+    Cout = wp.shape[0]
+    M, guard = B * (Y + 2) * (X + 2), X + 4
+    rows = torch.zeros(M + 2 * guard, Cin, dtype=x.dtype)
+    rows[guard:guard + M].view(B, Y + 2, X + 2, Cin)[:, 1:-1, 1:-1] = x.permute(0, 2, 3, 1)
+    out = torch.zeros(M, Cout, dtype=x.dtype)
+    for ky in range(3):
+        for kx in range(3):
+            off = (ky - 1) * (X + 2) + (kx - 1)
+            out += rows[guard + off:guard + off + M] @ wp[:, ky, kx].t()
+    return out.view(B, Y + 2, X + 2, Cout)[:, 1:-1, 1:-1].permute(0, 3, 1, 2)
+
+
+def test_pack_weight2d_dgrad_gives_the_input_gradient():
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(2, 5, 4, 6, generator=g, dtype=torch.float64, requires_grad=True)
+    w = torch.randn(7, 5, 3, 3, generator=g, dtype=torch.float64)
+    gout = torch.randn(2, 7, 4, 6, generator=g, dtype=torch.float64)
+    out = F.conv2d(x, w, padding=1)
+    out.backward(gout)
+    # the restatement is the forward conv on the forward packing ...
+    fwd = _padded_row_conv(x.detach(), w.permute(0, 2, 3, 1).contiguous())
+    assert ((fwd - out.detach()).norm() / out.detach().norm()).item() <= 1e-12
+    # ... and the input gradient on the dgrad packing
+    wd = conv3d_ops.pack_weight2d_dgrad(w)
+    assert tuple(wd.shape) == (5, 3, 3, 7) and wd.is_contiguous() and wd.dtype == w.dtype
+    got = _padded_row_conv(gout, wd)
+    assert ((got - x.grad).norm() / x.grad.norm()).item() <= 1e-12
+
+
+@pytest.mark.parametrize('gelu', [False, True])
+def test_closed_form_ln_backward_equals_autograd(gelu):
+    """ln_forward_ref / ln_gelu_backward_ref (what the kernels implement) against autograd
+    through nn.LayerNorm (of nn.GELU) in fp64: out, dx, dgamma, dbeta to 1e-10."""
+    g = torch.Generator().manual_seed(1)
+    C = 24
+    ln = nn.LayerNorm(C).double()
+    with torch.no_grad():
+        ln.weight.uniform_(0.5, 1.5, generator=g)
+        ln.bias.normal_(0, 0.2, generator=g)
+    x = (torch.randn(2, 7, C, generator=g, dtype=torch.float64) * 1.5 + 0.3).requires_grad_(True)
+    dout = torch.randn(2, 7, C, generator=g, dtype=torch.float64)
+    out = ln(nn.GELU()(x) if gelu else x)
+    out.backward(dout)
+    got, _, _ = conv3d_ops.ln_forward_ref(x.detach(), ln.weight.detach(), ln.bias.detach(),
+                                          ln.eps, gelu)
+    dx, dgamma, dbeta = conv3d_ops.ln_gelu_backward_ref(dout, x.detach(), ln.weight.detach(),
+                                                        ln.eps, gelu)
+
+    def close(p, q):
+        return ((p - q).norm() / q.norm()).item() <= 1e-10
+    assert close(got, out.detach()) and close(dx, x.grad)
+    assert close(dgamma, ln.weight.grad) and close(dbeta, ln.bias.grad)
+
+
+def test_switch_is_off_by_default_and_cpu_keeps_the_torch_definition():
+    assert ConvBlock.hip_train is False
+    torch.manual_seed(2)
+    blk = ConvBlock(64, 64).train()
+    x = torch.randn(1, 12, 64)
+    assert not blk._hip_train_ok(x)
+
+    def step(switch):
+        b = copy.deepcopy(blk)
+        xi = x.clone().requires_grad_(True)
+        ri = x.clone().requires_grad_(True)
+        ConvBlock.hip_train = switch
+        try:
+            assert not b._hip_train_ok(xi, ri)
+            out = b(xi, (3, 4), residual=ri)
+            out.square().sum().backward()
+        finally:
+            ConvBlock.hip_train = False
+        return [out.detach(), xi.grad, ri.grad] + [p.grad for p in b.parameters()]
+    for p, q in zip(step(False), step(True)):
+        assert torch.equal(p, q)

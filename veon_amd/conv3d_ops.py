@@ -366,6 +366,26 @@ class PaddedImage:
     def device(self):
         return self.storage.device
 
+    @classmethod
+    def from_storage(cls, storage, shape):
+        """The PaddedImage of ``shape`` on an existing storage tensor (guard rows
+        included), e.g. one that autograd saved."""
+        self = cls.__new__(cls)
+        self.shape = tuple(int(v) for v in shape)
+        B, C, Y, X = self.shape
+        self.guard = int(_lib.lib().veon_conv3d_guard_rows(Y, X))
+        self.M = B * (Y + 2) * (X + 2)
+        assert tuple(storage.shape) == (self.M + 2 * self.guard, C)
+        assert storage.is_contiguous() and storage.dtype == _half.dtype()
+        self.storage = storage
+        self.rows = storage[self.guard:self.guard + self.M]
+        return self
+
+    def interior(self):
+        """(B,Y,X,C) half view of the un-padded pixels."""
+        B, C, Y, X = self.shape
+        return self.rows.view(B, Y + 2, X + 2, C)[:, 1:-1, 1:-1]
+
 
 def pack_image(x, out=None):
     """(B,C,H,W) fp32 or bf16 -> PaddedImage."""
@@ -485,6 +505,118 @@ def image_layernorm(img, gamma, beta, eps, out=None, tokens=False, residual=None
     _lib.launch('veon_image_layernorm_bf16', dev, img.rows, gamma, beta, dst,
                 1 if tokens else 0, B, C, Y, X, float(eps), residual)
     return out
+
+
+# --------------------------------------------- training of the HSA ConvBlock (2-D)
+def pack_weight2d_dgrad(w):
+    """nn.Conv2d weight (Cout,Cin,3,3) -> the packed weight [Cin][2-ky][2-kx][Cout] with
+    which ``conv2d_k3`` of the output gradient is the INPUT gradient of the stride-1
+    pad-1 convolution (taps flipped, channel roles swapped).  Plain torch, any device;
+    the dtype follows ``w`` (the caller rounds to the half type)."""
+    assert w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)
+    return w.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous()
+
+
+def _cshape(v, t):
+    return v.view(*([1] * (t.dim() - 1)), -1)
+
+
+def ln_forward_ref(x, gamma, beta, eps, gelu=False):
+    """LayerNorm over the LAST axis of ``x`` (of GELU(x), erf form, with ``gelu``) in
+    plain torch, the mathematics the native passes implement: -> (out, xhat, rstd)."""
+    u = torch.nn.functional.gelu(x) if gelu else x
+    mean = u.mean(-1, keepdim=True)
+    rstd = ((u - mean).square().mean(-1, keepdim=True) + eps).rsqrt()
+    xhat = (u - mean) * rstd
+    return xhat * _cshape(gamma, x) + _cshape(beta, x), xhat, rstd
+
+
+def ln_gelu_backward_ref(dout, x, gamma, eps, gelu=False):
+    """The closed-form backward of ``ln_forward_ref``: -> (dx, dgamma, dbeta), the sums
+    taken over every axis but the last.  With ``gelu``, dx = du * GELU'(x),
+    GELU'(x) = Phi(x) + x phi(x)."""
+    _, xhat, rstd = ln_forward_ref(x, gamma, torch.zeros_like(gamma), eps, gelu)
+    a = dout * _cshape(gamma, x)
+    du = rstd * (a - a.mean(-1, keepdim=True) - xhat * (a * xhat).mean(-1, keepdim=True))
+    if gelu:
+        cdf = 0.5 * (1 + torch.erf(x * 2.0 ** -0.5))
+        pdf = torch.exp(-0.5 * x * x) * (2 * torch.pi) ** -0.5
+        du = du * (cdf + x * pdf)
+    red = list(range(x.dim() - 1))
+    return du, (dout * xhat).sum(red), dout.sum(red)
+
+
+def wgrad2d_workspace_bytes(B, Y, X, Cin, Cout):
+    """Bytes of split-K slabs ``conv2d_k3_wgrad`` needs (host-only); -1: unsupported."""
+    return int(_lib.lib().veon_conv2d_k3_wgrad_workspace_bytes(B, Y, X, Cin, Cout))
+
+
+def conv2d_k3_wgrad(dy, x, out=None):
+    """Weight gradient of the 3x3 stride-1 pad-1 convolution on PaddedImages: ``dy``
+    (Cout channels, halo zero), ``x`` (Cin) -> fp32 [Cout][3][3][Cin] (the layout of
+    ``pack_weight2d``).  Deterministic: split-K slabs added in a fixed order."""
+    dev = _lib.require_device(dy.storage, x.storage)
+    B, Cin, Y, X = x.shape
+    Cout = dy.shape[1]
+    assert dy.shape == (B, Cout, Y, X)
+    _lib.require_half(dy.rows, x.rows)
+    nbytes = wgrad2d_workspace_bytes(B, Y, X, Cin, Cout)
+    if nbytes < 0:
+        raise _lib.VeonHipError('conv2d_k3_wgrad: unsupported shape %s -> %d channels'
+                                % (x.shape, Cout))
+    ws = _workspace('wgrad2d', nbytes, dev, B, Y, X, Cin, Cout)
+    if out is None:
+        out = torch.empty((Cout, 3, 3, Cin), dtype=torch.float32, device=dev)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == Cout * 9 * Cin
+    _lib.launch('veon_conv2d_k3_wgrad_bf16', dev, dy.rows, x.rows, out, ws, nbytes,
+                B, Y, X, Cin, Cout)
+    return out
+
+
+def image_gelu_layernorm(img, gamma, beta, eps, out=None):
+    """LayerNorm(GELU(img)) over the channels of every pixel -> PaddedImage, zero halo."""
+    dev = _lib.require_device(img.storage, gamma, beta)
+    B, C, Y, X = img.shape
+    assert gamma.dtype == beta.dtype == torch.float32 and gamma.numel() == beta.numel() == C
+    assert gamma.is_contiguous() and beta.is_contiguous()
+    if out is None:
+        out = PaddedImage(B, C, Y, X, dev)
+    assert out.shape == img.shape and out is not img
+    _lib.launch('veon_image_gelu_layernorm_bf16', dev, img.rows, gamma, beta, out.rows,
+                B, C, Y, X, float(eps))
+    return out
+
+
+def image_layernorm_bwd(dout, x, gamma, eps, gelu_in=False):
+    """Backward of ``image_layernorm`` (``gelu_in``: of ``image_gelu_layernorm``) at its
+    stored input ``x`` (PaddedImage).  ``dout``: a PaddedImage or fp32 tokens
+    (B, Y*X, C).  -> (dx PaddedImage with a zero halo, sums fp32 (3, C)): sums[0] =
+    dgamma, sums[1] = dbeta, sums[2] = sum of dx over the pixels (the gradient of the
+    bias of the conv that produced ``x``)."""
+    B, C, Y, X = x.shape
+    tokens = torch.is_tensor(dout)
+    if tokens:
+        dev = _lib.require_device(dout, x.storage, gamma)
+        assert (dout.dtype == torch.float32 and dout.is_contiguous()
+                and tuple(dout.shape) == (B, Y * X, C))
+        src = dout
+    else:
+        dev = _lib.require_device(dout.storage, x.storage, gamma)
+        assert dout.shape == x.shape and dout is not x
+        _lib.require_half(dout.rows)
+        src = dout.rows
+    _lib.require_half(x.rows)
+    assert gamma.dtype == torch.float32 and gamma.numel() == C and gamma.is_contiguous()
+    nbytes = int(_lib.lib().veon_image_layernorm_bwd_workspace_bytes(C))
+    if nbytes < 0:
+        raise _lib.VeonHipError('image_layernorm_bwd: unsupported channel count %d' % C)
+    ws = _workspace('lnbwd', nbytes, dev, C)
+    dx = PaddedImage(B, C, Y, X, dev)
+    sums = torch.empty((3, C), dtype=torch.float32, device=dev)
+    _lib.launch('veon_image_layernorm_bwd_bf16', dev, src, 1 if tokens else 0, x.rows,
+                1 if gelu_in else 0, gamma, dx.rows, sums, ws, nbytes, B, C, Y, X,
+                float(eps))
+    return dx, sums
 
 
 def layernorm_tokens_to_image(x, gamma, beta, eps, out):

@@ -1,0 +1,396 @@
+// Training of the HSA network's ConvBlock (highres_side_adaptor.py:31-52) on the padded
+// channels-last half images of conv3d.hip's 2-D mode:
+//     y1 = conv1(a) + b1                      stored half, halo rows zero
+//     c  = LN1(GELU(y1))                      stored half, halo rows zero
+//     y2 = conv2(c) + b2                      stored half
+//     out = LN2(y2) (+ residual)              fp32 tokens (veon_image_layernorm_bf16)
+// and backwards, given dout (fp32 tokens):
+//     dy2 = LN2'(dout; y2)                    padded half, halo rows zero
+//     dW2[co][ky][kx][ci] = sum_rows dy2[row][co] * c[row + off(ky, kx)][ci]
+//     dc  = conv(dy2, flip(w2))               (veon_conv2d_k3_bf16 on a re-packed weight)
+//     dy1 = LN1'(dc; GELU(y1)) * GELU'(y1)    padded half, halo rows zero
+//     dW1 from (dy1, a), da = conv(dy1, flip(w1))
+// with the per-channel sums dgamma = sum dout * xhat, dbeta = sum dout and the conv
+// bias gradient db = sum dy of each LayerNorm backward pass.
+//
+// The weight gradient is the kernel of wgrad_kernel.h (shared with conv3d_train.hip) with
+// one ky per workgroup: tap (ky, kx) is the row offset (ky - 1)(X + 2) + (kx - 1), the
+// three kx taps read rows k - 1, k, k + 1 of one x slab.  Halo rows of dy are zero, so
+// the contraction over ALL padded rows is the interior's; where row + off leaves the
+// image it reads guard rows, which a PaddedImage allocates as zeros.
+//
+// The LayerNorm passes keep k_image_layernorm's layout: one wave per padded row, up to
+// two 16-byte chunks per lane (C <= 1024), statistics in fp32 and recomputed where
+// they are needed (nothing but the half images is stored between forward and backward).
+#include "mfma_common.h"
+#include "wgrad_kernel.h"
+
+namespace {
+
+struct Wgrad2dPlan { int wide, nco, nci, nsteps, split, sps; };
+
+bool wgrad2d_plan(int B, int Y, int X, int Cin, int Cout, Wgrad2dPlan* pl) {
+  if (B <= 0 || Y <= 0 || X <= 0 || Cin <= 0 || Cout <= 0 || Cin % 64 != 0 ||
+      Cout % 64 != 0)
+    return false;
+  const int64_t M = (int64_t)B * (Y + 2) * (X + 2);
+  const int64_t cmax = Cin > Cout ? Cin : Cout;
+  // 32-bit byte offsets of the LDS DMA, as in conv3d.hip
+  if ((M + 2 * veon_conv3d_guard_rows(Y, X)) * cmax >= 0x3fffffffLL) return false;
+  pl->wide = (Cin % 128 == 0 && Cout % 128 == 0) ? 1 : 0;
+  const int tile = pl->wide ? 128 : 64;
+  pl->nco = Cout / tile;
+  pl->nci = Cin / tile;
+  pl->nsteps = (int)((M + WBK - 1) / WBK);
+  // The split rule of conv3d_train.hip with 3 (ky) instead of 9 (kz, ky) workgroups per
+  // tile: one round of the 256 CUs, at least 8 slabs of rows per split.  The HSA
+  // ConvBlock (384 -> 384, M = 70 488): 27 tiles x 9 = 243.
+  const int tiles = 3 * pl->nco * pl->nci;
+  int split = kNumCU / tiles;
+  if (split > pl->nsteps / 8) split = pl->nsteps / 8;
+  if (split < 1) split = 1;
+  pl->sps = (pl->nsteps + split - 1) / split;
+  pl->split = (pl->nsteps + pl->sps - 1) / pl->sps;   // no empty split
+  return true;
+}
+
+// ------------------------------------------------------------------ LayerNorm passes
+// GELU (erf form) and its derivative from one erfc evaluation, the approximation of
+// gelu_erf (mfma_common.h; |error| of Phi <= 8e-8):
+//   h = erfc(|y| / sqrt 2) / 2,  Phi(y) = y > 0 ? 1 - h : h,  phi(y) = exp(-y^2 / 2) / sqrt(2 pi)
+//   GELU(y) = y Phi(y) = max(y, 0) - |y| h,  GELU'(y) = Phi(y) + y phi(y)
+__device__ __forceinline__ void gelu_and_slope(float y, float* g, float* dg) {
+  const float ay = fabsf(y);
+  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, ay, 1.f));
+  float p = fmaf(0.5f * 1.061405429f, t, 0.5f * -1.453152027f);
+  p = fmaf(p, t, 0.5f * 1.421413741f);
+  p = fmaf(p, t, 0.5f * -0.284496736f);
+  p = fmaf(p, t, 0.5f * 0.254829592f);
+  const float e = __builtin_amdgcn_exp2f(ay * ay * -0.72134752044448170f);
+  const float h = (p * t) * e;
+  *g = fmaxf(y, 0.f) - ay * h;
+  *dg = fmaf(y * 0.39894228040143268f, e, y > 0.f ? 1.f - h : h);
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// A lane holds N (1: C <= 512, 2: C <= 1024) 16-byte chunks of a padded row: channels
+// 8 (lane + 64 h) + 0..7, h < N; has[h]: the row is wide enough for that chunk.
+// One padded row of the wave as fp32, zeros where the lane has no chunk.
+template <int N>
+__device__ __forceinline__ void load_row(const bf16_t* p, int lane, const bool* has,
+                                         float* v) {
+#pragma unroll
+  for (int h = 0; h < N; ++h) {
+    bf16x8 c = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (has[h]) c = *reinterpret_cast<const bf16x8*>(p + (lane + 64 * h) * 8);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[8 * h + k] = bf2f((bf16_t)c[k]);
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void store_row(bf16_t* p, int lane, const bool* has,
+                                          const float* v) {
+#pragma unroll
+  for (int h = 0; h < N; ++h) {
+    if (!has[h]) continue;
+    bf16x8 o8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o8[k] = (short)f2bf(v[8 * h + k]);
+    *reinterpret_cast<bf16x8*>(p + (lane + 64 * h) * 8) = o8;
+  }
+}
+
+// mean and rstd of the lane-distributed row u (entries of absent chunks are ignored)
+template <int N>
+__device__ __forceinline__ void row_stats(const float* u, const bool* has, int C, float eps,
+                                          float* mean, float* rstd) {
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8 * N; ++k) sum += has[k >> 3] ? u[k] : 0.f;
+  *mean = wave_sum(sum) / C;
+  float sq = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8 * N; ++k) {
+    const float a = has[k >> 3] ? u[k] - *mean : 0.f;
+    sq = fmaf(a, a, sq);
+  }
+  *rstd = rsqrtf(wave_sum(sq) / C + eps);
+}
+
+// out = LN(GELU(in)) on interior rows, zeros on halo rows
+__global__ __launch_bounds__(256) void k_image_gelu_layernorm(
+    const bf16_t* __restrict__ in, const float* __restrict__ gamma,
+    const float* __restrict__ beta, bf16_t* __restrict__ out, int B, int Y, int X, int C,
+    float eps) {
+  const int lane = threadIdx.x & 63;
+  const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int Yp = Y + 2, Xp = X + 2;
+  if (m >= (int64_t)B * Yp * Xp) return;
+  const int x = (int)(m % Xp), y = (int)((m / Xp) % Yp);
+  const int nchunk = C / 8;
+  const bool has[2] = {lane < nchunk, lane + 64 < nchunk};
+  float v[16];
+  if (x >= 1 && x <= X && y >= 1 && y <= Y) {
+    load_row<2>(in + m * C, lane, has, v);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      float slope;
+      gelu_and_slope(v[k], &v[k], &slope);
+    }
+    float mean, rstd;
+    row_stats<2>(v, has, C, eps, &mean, &rstd);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      if (!has[h]) continue;
+      const int c0 = (lane + 64 * h) * 8;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        v[8 * h + k] = (v[8 * h + k] - mean) * rstd * gamma[c0 + k] + beta[c0 + k];
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = 0.f;
+  }
+  store_row<2>(out + m * C, lane, has, v);
+}
+
+constexpr int kLnBlocks = 1024;   // partial sums of stage one (upper bound)
+
+// LayerNorm backward (optionally through GELU in front of it), stage one of the sums.
+// Workgroup b walks padded rows [b rows_per_block, (b + 1) rows_per_block), wave w of it
+// rows w, w + 4, ...: per interior row, with u = GELU(x) or x,
+//   xhat = (u - mean) rstd,  a = dout gamma,  du = rstd (a - mean(a) - xhat mean(a xhat))
+//   dx = du GELU'(x)  or  du
+// written as half (halo rows: zeros), and every lane keeps the running sums of its 8 N
+// channels: dout xhat, dout, dx (fp32, before dx is rounded).  At the end the four waves
+// are added in wave order and part[b][3][C] is written.
+template <bool GELU_IN, bool DOUT_TOKENS, int N>
+__global__ __launch_bounds__(256) void k_image_layernorm_bwd(
+    const void* __restrict__ dout, const bf16_t* __restrict__ xin,
+    const float* __restrict__ gamma, bf16_t* __restrict__ dx, float* __restrict__ part,
+    int B, int Y, int X, int C, float eps, int rows_per_block) {
+  constexpr int E = 8 * N;                 // channels per lane
+  __shared__ float red[3][3 * E * 64];     // waves 1..3: [sum * E + k][lane]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int Yp = Y + 2, Xp = X + 2;
+  const int64_t M = (int64_t)B * Yp * Xp;
+  const int nchunk = C / 8;
+  const bool has[2] = {lane < nchunk, N == 2 && lane + 64 < nchunk};
+  float gm[E], acc[3 * E];
+#pragma unroll
+  for (int k = 0; k < E; ++k)
+    gm[k] = has[k >> 3] ? gamma[(lane + 64 * (k >> 3)) * 8 + (k & 7)] : 0.f;
+#pragma unroll
+  for (int k = 0; k < 3 * E; ++k) acc[k] = 0.f;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < M ? r0 + rows_per_block : M;
+  for (int64_t m = r0 + wave; m < r1; m += 4) {
+    const int x = (int)(m % Xp), y = (int)((m / Xp) % Yp), b = (int)(m / ((int64_t)Xp * Yp));
+    float u[E], d[E], slope[E];
+    (void)b;   // the token index of DOUT_TOKENS only
+    if (x >= 1 && x <= X && y >= 1 && y <= Y) {   // wave-uniform
+      load_row<N>(xin + m * C, lane, has, u);
+      if (DOUT_TOKENS) {
+        const float* p = static_cast<const float*>(dout) +
+                         (((int64_t)b * Y + (y - 1)) * X + (x - 1)) * C;
+#pragma unroll
+        for (int h = 0; h < N; ++h) {
+          float4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
+          if (has[h]) {
+            lo = *reinterpret_cast<const float4*>(p + (lane + 64 * h) * 8);
+            hi = *reinterpret_cast<const float4*>(p + (lane + 64 * h) * 8 + 4);
+          }
+          d[8 * h + 0] = lo.x; d[8 * h + 1] = lo.y; d[8 * h + 2] = lo.z; d[8 * h + 3] = lo.w;
+          d[8 * h + 4] = hi.x; d[8 * h + 5] = hi.y; d[8 * h + 6] = hi.z; d[8 * h + 7] = hi.w;
+        }
+      } else {
+        load_row<N>(static_cast<const bf16_t*>(dout) + m * C, lane, has, d);
+      }
+      if (GELU_IN) {
+#pragma unroll
+        for (int k = 0; k < E; ++k) gelu_and_slope(u[k], &u[k], &slope[k]);
+      }
+      float mean, rstd;
+      row_stats<N>(u, has, C, eps, &mean, &rstd);
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        // absent chunks: d = gm = 0, so they add nothing to any sum
+        u[k] = (u[k] - mean) * rstd;          // xhat
+        const float a = d[k] * gm[k];
+        s1 += a;
+        s2 = fmaf(a, u[k], s2);
+      }
+      s1 = wave_sum(s1) / C;
+      s2 = wave_sum(s2) / C;
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        float g = rstd * (d[k] * gm[k] - s1 - u[k] * s2);
+        if (GELU_IN) g *= slope[k];
+        acc[k] = fmaf(d[k], u[k], acc[k]);
+        acc[E + k] += d[k];
+        acc[2 * E + k] += g;
+        d[k] = g;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < E; ++k) d[k] = 0.f;
+    }
+    store_row<N>(dx + m * C, lane, has, d);
+  }
+  if (wave > 0) {
+#pragma unroll
+    for (int k = 0; k < 3 * E; ++k) red[wave - 1][k * 64 + lane] = acc[k];
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int k = 0; k < 3 * E; ++k)
+      acc[k] = ((acc[k] + red[0][k * 64 + lane]) + red[1][k * 64 + lane]) + red[2][k * 64 + lane];
+    float* o = part + (int64_t)blockIdx.x * 3 * C;
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+      for (int h = 0; h < N; ++h) {
+        if (!has[h]) continue;
+        float* q = o + s * C + (lane + 64 * h) * 8;
+        const float* a = acc + E * s + 8 * h;
+        *reinterpret_cast<float4*>(q) = float4{a[0], a[1], a[2], a[3]};
+        *reinterpret_cast<float4*>(q + 4) = float4{a[4], a[5], a[6], a[7]};
+      }
+  }
+}
+
+// Stage two: one wave per float4 of sums[3][C].  Lane l adds the partials of workgroups
+// l, l + 64, ... in that order, then the 64 lanes are added by a butterfly: a fixed
+// order for a fixed number of workgroups, and log-depth instead of a serial walk.
+__global__ __launch_bounds__(256) void k_ln_sums_final(const float4* __restrict__ part,
+                                                       float4* __restrict__ sums, int n4,
+                                                       int nblocks) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n4) return;   // wave-uniform
+  float4 s = {0.f, 0.f, 0.f, 0.f};
+  for (int b = lane; b < nblocks; b += 64) {
+    const float4 v = part[(int64_t)b * n4 + i];
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  s.x = wave_sum(s.x); s.y = wave_sum(s.y); s.z = wave_sum(s.z); s.w = wave_sum(s.w);
+  if (lane == 0) sums[i] = s;
+}
+
+bool ln_shape_ok(int B, int C, int Y, int X) {
+  return B > 0 && Y > 0 && X > 0 && C > 0 && C % 8 == 0 && C <= 1024 &&
+         ((int64_t)B * (Y + 2) * (X + 2) + 3) / 4 <= 0x7fffffffLL;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t veon_conv2d_k3_wgrad_workspace_bytes(int B, int Y, int X, int Cin, int Cout) {
+  Wgrad2dPlan pl;
+  if (!wgrad2d_plan(B, Y, X, Cin, Cout, &pl)) return -1;
+  return (int64_t)pl.split * Cout * 9 * Cin * (int64_t)sizeof(float);
+}
+
+int veon_conv2d_k3_wgrad_bf16(const void* dy_padded, const void* x_padded, float* dw,
+                              void* workspace, int64_t workspace_bytes, int B, int Y,
+                              int X, int Cin, int Cout, void* stream) {
+  Wgrad2dPlan pl;
+  if (!wgrad2d_plan(B, Y, X, Cin, Cout, &pl)) return VEON_ERR_BAD_ARG;
+  if (!dy_padded || !x_padded || !dw || !workspace || !al16(dy_padded) ||
+      !al16(x_padded) || !al16(dw) || !al16(workspace))
+    return VEON_ERR_BAD_ARG;
+  const int64_t n = (int64_t)Cout * 9 * Cin;
+  if (workspace_bytes < pl.split * n * (int64_t)sizeof(float)) return VEON_ERR_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bf16_t* D = static_cast<const bf16_t*>(dy_padded);
+  const bf16_t* Xv = static_cast<const bf16_t*>(x_padded);
+  float* ws = static_cast<float*>(workspace);
+  const dim3 grid((unsigned)(3 * pl.nco * pl.nci), (unsigned)pl.split);
+#define VEON_LAUNCH_WGRAD2D(TI, TJ)                                                     \
+  do {                                                                                  \
+    constexpr int chx = 32 * TJ / 8, rpx = 64 / chx;                                    \
+    constexpr int lds = 2 * (WBK * 32 * TI + (WBK + 2 + rpx - 1) / rpx * rpx * 32 * TJ) \
+                        * (int)sizeof(bf16_t);                                          \
+    static const hipError_t attr = hipFuncSetAttribute(                                 \
+        reinterpret_cast<const void*>(&k_conv_k3_wgrad<TI, TJ, 3>),                     \
+        hipFuncAttributeMaxDynamicSharedMemorySize, lds);                               \
+    if (attr != hipSuccess) return VEON_ERR_LAUNCH;                                     \
+    hipLaunchKernelGGL((k_conv_k3_wgrad<TI, TJ, 3>), grid, dim3(256), lds, s, D, Xv,    \
+                       ws, Y + 2, X + 2, Cin, Cout, pl.nsteps, pl.sps, pl.nco, pl.nci); \
+  } while (0)
+  if (pl.wide) VEON_LAUNCH_WGRAD2D(4, 4); else VEON_LAUNCH_WGRAD2D(2, 2);
+#undef VEON_LAUNCH_WGRAD2D
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0,
+                     s, reinterpret_cast<const float4*>(ws), reinterpret_cast<float4*>(dw),
+                     n / 4, pl.split);
+  return launch_status();
+}
+
+int veon_image_gelu_layernorm_bf16(const void* in_padded, const float* gamma,
+                                   const float* beta, void* out_padded, int B, int C,
+                                   int Y, int X, float eps, void* stream) {
+  if (!ln_shape_ok(B, C, Y, X) || !in_padded || !gamma || !beta || !out_padded ||
+      in_padded == out_padded || !al16(in_padded) || !al16(out_padded))
+    return VEON_ERR_BAD_ARG;
+  const int64_t M = (int64_t)B * (Y + 2) * (X + 2);
+  hipLaunchKernelGGL(k_image_gelu_layernorm, dim3((unsigned)((M + 3) / 4)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream),
+                     static_cast<const bf16_t*>(in_padded), gamma, beta,
+                     static_cast<bf16_t*>(out_padded), B, Y, X, C, eps);
+  return launch_status();
+}
+
+int64_t veon_image_layernorm_bwd_workspace_bytes(int C) {
+  if (C <= 0 || C % 8 != 0 || C > 1024) return -1;
+  return (int64_t)kLnBlocks * 3 * C * (int64_t)sizeof(float);
+}
+
+int veon_image_layernorm_bwd_bf16(const void* dout, int dout_tokens_f32,
+                                  const void* x_padded, int gelu_in, const float* gamma,
+                                  void* dx_padded, float* sums, void* workspace,
+                                  int64_t workspace_bytes, int B, int C, int Y, int X,
+                                  float eps, void* stream) {
+  if (!ln_shape_ok(B, C, Y, X) || !dout || !x_padded || !gamma || !dx_padded || !sums ||
+      !workspace || dx_padded == dout || dx_padded == x_padded || !al16(dout) ||
+      !al16(x_padded) || !al16(dx_padded) || !al16(sums) || !al16(workspace))
+    return VEON_ERR_BAD_ARG;
+  if (workspace_bytes < veon_image_layernorm_bwd_workspace_bytes(C)) return VEON_ERR_WORKSPACE;
+  const int64_t M = (int64_t)B * (Y + 2) * (X + 2);
+  // at least two rounds of rows per workgroup, at most kLnBlocks workgroups
+  int64_t rows = (M + kLnBlocks - 1) / kLnBlocks;
+  if (rows < 8) rows = 8;
+  const int nblocks = (int)((M + rows - 1) / rows);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bf16_t* px = static_cast<const bf16_t*>(x_padded);
+  bf16_t* pd = static_cast<bf16_t*>(dx_padded);
+  float* part = static_cast<float*>(workspace);
+  // one 16-byte chunk per lane up to 512 channels (half the registers), two above
+#define VEON_LN_BWD(GE, TK)                                                              \
+  do {                                                                                   \
+    if (C <= 512)                                                                        \
+      hipLaunchKernelGGL((k_image_layernorm_bwd<GE, TK, 1>), dim3(nblocks), dim3(256), 0, \
+                         s, dout, px, gamma, pd, part, B, Y, X, C, eps, (int)rows);      \
+    else                                                                                 \
+      hipLaunchKernelGGL((k_image_layernorm_bwd<GE, TK, 2>), dim3(nblocks), dim3(256), 0, \
+                         s, dout, px, gamma, pd, part, B, Y, X, C, eps, (int)rows);      \
+  } while (0)
+  if (gelu_in) { if (dout_tokens_f32) VEON_LN_BWD(true, true); else VEON_LN_BWD(true, false); }
+  else         { if (dout_tokens_f32) VEON_LN_BWD(false, true); else VEON_LN_BWD(false, false); }
+#undef VEON_LN_BWD
+  const int n4 = 3 * C / 4;
+  hipLaunchKernelGGL(k_ln_sums_final, dim3((n4 + 3) / 4), dim3(256), 0, s,
+                     reinterpret_cast<const float4*>(part), reinterpret_cast<float4*>(sums),
+                     n4, nblocks);
+  return launch_status();
+}
+
+}  // extern "C"

@@ -1,0 +1,186 @@
+// The weight gradient of the 3x3 and 3x3x3 stride-1 pad-1 convolutions on padded
+// channels-last half rows: ONE kernel body for conv3d_train.hip (27 taps, one (kz, ky)
+// pair per workgroup) and conv2d_train.hip (9 taps, one ky per workgroup).  A tap is a
+// constant row offset in both layouts, so the two differ only in how the workgroup's
+// index becomes that offset and in the tap count of the output slab; the contraction
+// and its accumulation order are the same code.  Included inside each file's
+// translation unit after mfma_common.h.
+#pragma once
+#include "mfma_common.h"
+
+namespace {
+
+
+typedef bf16x4 __attribute__((address_space(3))) lds_bf16x4;
+
+constexpr int WBK = 64;   // rows of the contraction per LDS slab
+
+// XOR key of the 16-byte chunks of an LDS row holding `chunks` (8 or 16) of them; for
+// 256-byte rows the image of the programming guide's transposed-read section.  Applied
+// on the DMA source address and again on the fragment read, per lane and per chunk.
+__device__ __forceinline__ int tr_key(int row, int chunks) {
+  return (((row & 3) << 2) | ((row >> 2) & 3)) & (chunks - 1);
+}
+
+// Cout tile = 32 TI, Cin tile = 32 TJ; 2 x 2 waves of (16 TI) x (16 TJ) x 3 taps each.
+// NZY = 9: 3-D grid, the workgroup's zy = 3 (dz + 1) + (dy + 1); NZY = 3: 2-D images
+// (Yp is unused), zy = dy + 1.  The slab is [Cout][3 NZY][Cin].
+template <int TI, int TJ, int NZY>
+__global__ __launch_bounds__(256) void k_conv_k3_wgrad(
+    const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, float* __restrict__ ws,
+    int Yp, int Xp, int Cin, int Cout, int nsteps, int steps_per_split, int nco, int nci) {
+  constexpr int CO_T = 32 * TI, CI_T = 32 * TJ;
+  constexpr int CHD = CO_T / 8, CHX = CI_T / 8;      // 16-byte chunks per LDS row
+  constexpr int RPD = 64 / CHD, RPX = 64 / CHX;      // rows per 1 KiB DMA piece
+  constexpr int DPIECES = WBK / RPD;
+  constexpr int XPIECES = (WBK + 2 + RPX - 1) / RPX;  // rows k0 - 1 .. k0 + 64
+  constexpr int D_ELEMS = WBK * CO_T, X_ELEMS = XPIECES * RPX * CI_T;
+  constexpr int BUF_ELEMS = D_ELEMS + X_ELEMS;
+  constexpr int DP = (DPIECES + 3) / 4, XP = (XPIECES + 3) / 4;
+  extern __shared__ __attribute__((aligned(16))) bf16_t smem[];   // [2][dy | x]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wco = wave >> 1, wci = wave & 1;
+  const int fr = lane & 15, fg = lane >> 4;
+
+  int t = blockIdx.x;
+  const int ci_t = t % nci; t /= nci;
+  const int co_t = t % nco;
+  const int zy = t / nco;                     // 3 (dz + 1) + (dy + 1), or dy + 1
+  const int split = blockIdx.y;
+  const int s0 = split * steps_per_split;
+  const int s1 = s0 + steps_per_split < nsteps ? s0 + steps_per_split : nsteps;
+
+  // LDS row j of the x slab of step s holds padded row 64 s + j + offrow; tap dx reads
+  // slab rows k + dx.  Rows outside [0, M) are guard rows (zeros).
+  const int offrow =
+      NZY == 9 ? ((zy / 3 - 1) * Yp + (zy % 3 - 1)) * Xp - 1 : (zy - 1) * Xp - 1;
+  const rsrc_t rsD = make_rsrc(dy + co_t * CO_T);
+  const rsrc_t rsX = make_rsrc(x + (int64_t)offrow * Cin + ci_t * CI_T);
+  int srcD[DP], srcX[XP];
+#pragma unroll
+  for (int j = 0; j < DP; ++j) {
+    const int r = (wave + 4 * j) * RPD + lane / CHD;
+    const int c = (lane % CHD) ^ tr_key(r, CHD);
+    srcD[j] = 2 * (r * Cout + c * 8);
+  }
+#pragma unroll
+  for (int j = 0; j < XP; ++j) {
+    const int r = (wave + 4 * j) * RPX + lane / CHX;
+    const int c = (lane % CHX) ^ tr_key(r, CHX);
+    srcX[j] = 2 * (r * Cin + c * 8);
+  }
+  auto dma = [&](int buf, int step) {
+    bf16_t* dD = smem + buf * BUF_ELEMS;
+    bf16_t* dX = dD + D_ELEMS;
+    const int k0 = step * WBK;
+#pragma unroll
+    for (int j = 0; j < DP; ++j)
+      if (wave + 4 * j < DPIECES)   // wave-uniform
+        buffer_load_lds16(rsD, (lptr_t)(dD + (wave + 4 * j) * 512), srcD[j],
+                          2 * k0 * Cout);
+#pragma unroll
+    for (int j = 0; j < XP; ++j)
+      if (wave + 4 * j < XPIECES)
+        buffer_load_lds16(rsX, (lptr_t)(dX + (wave + 4 * j) * 512), srcX[j],
+                          2 * k0 * Cin);
+  };
+
+  // transposed-read offsets (elements): lane 4q + p of a 16-lane group addresses row q,
+  // columns 4p .. 4p + 3 of its 4 x 16 block and receives column fr of the four rows
+  const int q = fr >> 2, p = fr & 3;
+  const int rbase = 8 * (fg & 1) + 4 * (fg >> 1) + q;   // + 16 per read, + 32 per k-step
+  int offD[TI], offX[3][TJ];
+#pragma unroll
+  for (int i = 0; i < TI; ++i) {
+    const int ch = wco * 2 * TI + 2 * i + (p >> 1);
+    offD[i] = rbase * CO_T + ((ch ^ tr_key(rbase, CHD)) * 8) + 4 * (p & 1);
+  }
+#pragma unroll
+  for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) {
+      const int ch = wci * 2 * TJ + 2 * j + (p >> 1);
+      // the key reads bits 0..3 of the row: unchanged by the + 16 / + 32 of the reads
+      offX[dx][j] = (rbase + dx) * CI_T + ((ch ^ tr_key(rbase + dx, CHX)) * 8) + 4 * (p & 1);
+    }
+
+  f32x4 acc[3][TI][TJ];
+#pragma unroll
+  for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) acc[dx][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  auto frag = [&](const bf16_t* base, int stride16) {
+    const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)base);
+    const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + stride16));
+    bf16x8 f;
+    f[0] = v0[0]; f[1] = v0[1]; f[2] = v0[2]; f[3] = v0[3];
+    f[4] = v1[0]; f[5] = v1[1]; f[6] = v1[2]; f[7] = v1[3];
+    return f;
+  };
+  auto compute = [&](int buf) {
+    const bf16_t* tD = smem + buf * BUF_ELEMS;
+    const bf16_t* tX = tD + D_ELEMS;
+#pragma unroll
+    for (int ks = 0; ks < WBK / 32; ++ks) {
+      bf16x8 fd[TI];
+#pragma unroll
+      for (int i = 0; i < TI; ++i)
+        fd[i] = frag(tD + offD[i] + ks * 32 * CO_T, 16 * CO_T);
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) {
+          const bf16x8 fx = frag(tX + offX[dx][j] + ks * 32 * CI_T, 16 * CI_T);
+#pragma unroll
+          for (int i = 0; i < TI; ++i)
+            // acc[dx][i][j][reg] = dW[co 16 i + 4 fg + reg][tap dx][ci 16 j + fr]
+            acc[dx][i][j] = mfma_16x16x32(fd[i], fx, acc[dx][i][j]);
+        }
+    }
+  };
+
+  if (s0 < s1) {   // workgroup-uniform; every lane stays active for the transposed reads
+    dma(0, s0);
+    __syncthreads();
+    for (int st = s0; st < s1; ++st) {
+      const int buf = (st - s0) & 1;
+      if (st + 1 < s1) dma(buf ^ 1, st + 1);
+      compute(buf);
+      __syncthreads();   // next slab landed (vmcnt drained) and this one released
+    }
+  }
+
+  // partial tile -> this split's slab [Cout][3 NZY][Cin], plain stores (64 B per 16 lanes)
+  float* slab = ws + (int64_t)split * Cout * (3 * NZY) * Cin;
+#pragma unroll
+  for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+      for (int j = 0; j < TJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int co = co_t * CO_T + wco * 16 * TI + 16 * i + 4 * fg + r;
+          const int ci = ci_t * CI_T + wci * 16 * TJ + 16 * j + fr;
+          slab[((int64_t)co * (3 * NZY) + zy * 3 + dx) * Cin + ci] = acc[dx][i][j][r];
+        }
+}
+
+// dW = slab 0 + slab 1 + ... in index order
+__global__ __launch_bounds__(256) void k_wgrad_reduce(const float4* __restrict__ ws,
+                                                      float4* __restrict__ dw, int64_t n4,
+                                                      int split) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  float4 s = ws[i];
+  for (int k = 1; k < split; ++k) {
+    const float4 v = ws[(int64_t)k * n4 + i];
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  dw[i] = s;
+}
+
+}  // namespace

@@ -101,11 +101,84 @@ class FeedForward(NativeCacheMixin, nn.Module):
         return y.view(B, h * w, -1).permute(0, 2, 1).float().contiguous().view(B, -1, h, w)
 
 
+class _ConvBlockTrainFn(torch.autograd.Function):
+    """One training step of ``ConvBlock`` on padded images (csrc/conv2d_train.hip):
+    fp32 tokens in, fp32 tokens out, parameter gradients in fp32 in the parameters' own
+    layout.  Saved for backward: the four padded half images a (input), y1 = conv1 + b1,
+    c = LN1(GELU(y1)), y2 = conv2 + b2; row statistics and GELU are recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, residual, w1, b1, g1, e1, w2, b2, g2, e2, size, eps1, eps2):
+        B, L, dim = x.shape
+        H, W = size
+        dev = x.device
+        a = conv3d_ops.PaddedImage(B, dim, H, W, dev)
+        # tokens are channels-last already: one strided copy into the interior
+        a.interior().copy_(x.detach().view(B, H, W, dim))
+        # the half copies of the weights are re-packed from the fp32 parameters every step
+        y1 = conv3d_ops.conv2d_k3(a, conv3d_ops.pack_weight2d(w1), None,
+                                  b1.detach().float().contiguous())
+        c = conv3d_ops.image_gelu_layernorm(y1, g1.detach().contiguous(),
+                                            e1.detach().contiguous(), eps1)
+        y2 = conv3d_ops.conv2d_k3(c, conv3d_ops.pack_weight2d(w2), None,
+                                  b2.detach().float().contiguous())
+        if residual is not None:
+            residual = residual.detach().contiguous().view(B, L, -1)
+        out = conv3d_ops.image_layernorm(y2, g2.detach().contiguous(),
+                                         e2.detach().contiguous(), eps2, tokens=True,
+                                         residual=residual)
+        ctx.shapes = (a.shape, y1.shape, y2.shape)
+        ctx.eps = (eps1, eps2)
+        ctx.half = _half.dtype()
+        ctx.save_for_backward(a.storage, y1.storage, c.storage, y2.storage, w1, g1, w2, g2)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        a_s, y1_s, c_s, y2_s, w1, g1, w2, g2 = ctx.saved_tensors
+        sa, s1, s2 = ctx.shapes
+        img = conv3d_ops.PaddedImage.from_storage
+        a, y1, c, y2 = img(a_s, sa), img(y1_s, s1), img(c_s, s1), img(y2_s, s2)
+        need = ctx.needs_input_grad
+        dout = dout.contiguous()
+        # LN2 backwards from the fp32 tokens, then conv2's two gradients
+        dy2, t2 = conv3d_ops.image_layernorm_bwd(dout, y2, g2.detach().contiguous(),
+                                                 ctx.eps[1])
+        dw2 = conv3d_ops.conv2d_k3_wgrad(dy2, c) if need[6] else None
+        dc = conv3d_ops.conv2d_k3(dy2, conv3d_ops.pack_weight2d_dgrad(w2).to(ctx.half))
+        # LN1 and GELU backwards at the stored pre-activation, then conv1's gradients
+        dy1, t1 = conv3d_ops.image_layernorm_bwd(dc, y1, g1.detach().contiguous(),
+                                                 ctx.eps[0], gelu_in=True)
+        dw1 = conv3d_ops.conv2d_k3_wgrad(dy1, a) if need[2] else None
+        dx = None
+        if need[0]:
+            da = conv3d_ops.conv2d_k3(dy1, conv3d_ops.pack_weight2d_dgrad(w1).to(ctx.half))
+            B, dim, H, W = sa
+            dx = da.interior().float().reshape(B, H * W, dim)
+
+        def wgrad(dw, w):    # [Cout][3][3][Cin] -> the parameter's layout and dtype
+            return None if dw is None else dw.permute(0, 3, 1, 2).to(w.dtype)
+        return (dx, dout if need[1] else None,
+                wgrad(dw1, w1), t1[2].to(w1.dtype), t1[0].to(g1.dtype), t1[1].to(g1.dtype),
+                wgrad(dw2, w2), t2[2].to(w2.dtype), t2[0].to(g2.dtype), t2[1].to(g2.dtype),
+                None, None, None)
+
+
 class ConvBlock(NativeCacheMixin, nn.Module):
     _native_cache = ('_hip',)
 
     """tokens (B, L, dim) on an H x W map: conv3x3 -> GELU -> LN -> conv3x3 -> LN
-    (:31-52)."""
+    (:31-52).
+
+    ``hip_train`` (class attribute, default False): opt-in native TRAINING path.  When
+    set, a training-mode block under autograd on ROCm fp32 tokens whose widths the
+    kernels support runs ``_ConvBlockTrainFn`` (MFMA convs, data and weight gradients,
+    LayerNorm and GELU backwards in HIP); anything else takes the code below unchanged.
+    It does not depend on ``conv_dtype``.  ``pre_ln`` stays torch under autograd: the
+    function's input is the tokens after it."""
+
+    hip_train = False
 
     def __init__(self, dim, hidden_dim, out_dim=-1):
         super().__init__()
@@ -123,6 +196,40 @@ class ConvBlock(NativeCacheMixin, nn.Module):
                 and not torch.is_grad_enabled() and not self.training
                 and self.dim % 64 == 0 and self.h_dim % 64 == 0
                 and self.h_dim % 8 == 0 and self.out_dim % 8 == 0)
+
+    def _hip_train_ok(self, x, residual=None):
+        """The native training path's own test: the switch, training mode under autograd,
+        ROCm fp32 tokens, widths the weight gradient takes (multiples of 64; the LayerNorm
+        passes hold rows up to 1024 wide), both convs 3x3 stride 1 pad 1 with bias, both
+        LayerNorms affine, fp32 parameters."""
+        if not (self.hip_train and self.training and torch.is_grad_enabled()
+                and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 3):
+            return False
+        if residual is not None and not (
+                residual.is_cuda and residual.dtype == torch.float32
+                and residual.shape[-1] == self.out_dim
+                and residual.numel() == x.shape[0] * x.shape[1] * self.out_dim):
+            return False
+        convs, lns = (self.conv1, self.conv2), (self.ln1, self.ln2)
+        return (all(d % 64 == 0 and d <= 1024 for d in (self.dim, self.h_dim, self.out_dim))
+                and all(isinstance(c, nn.Conv2d) and c.kernel_size == (3, 3)
+                        and c.stride == (1, 1) and c.padding == (1, 1)
+                        and c.dilation == (1, 1) and c.groups == 1
+                        and c.padding_mode == 'zeros' and c.bias is not None
+                        and c.weight.dtype == torch.float32 for c in convs)
+                and all(isinstance(ln, nn.LayerNorm) and ln.weight is not None
+                        and ln.bias is not None and ln.weight.dtype == torch.float32
+                        and len(ln.normalized_shape) == 1 for ln in lns)
+                and isinstance(self.gelu, nn.GELU)
+                and getattr(self.gelu, 'approximate', 'none') == 'none')
+
+    def _train_native(self, x, size, residual=None):
+        c1, c2, l1, l2 = self.conv1, self.conv2, self.ln1, self.ln2
+        return _ConvBlockTrainFn.apply(
+            x.contiguous(), residual, c1.weight, c1.bias, l1.weight, l1.bias,
+            c2.weight, c2.bias, l2.weight, l2.bias, (int(size[0]), int(size[1])),
+            l1.eps, l2.eps)
 
     def _hip_forward(self, x, size, residual=None, pre_ln=None):
         B, L, _ = x.shape
@@ -178,6 +285,8 @@ class ConvBlock(NativeCacheMixin, nn.Module):
             return self._hip_forward(x, size, residual, pre_ln)
         if pre_ln is not None:
             x = pre_ln(x)
+        if self._hip_train_ok(x, residual):
+            return self._train_native(x, size, residual)
         if residual is not None:
             return self.forward(x, size) + residual
         x = x.permute(0, 2, 1).reshape(B, dim, H, W).contiguous()
