@@ -380,7 +380,10 @@ int veon_lidar_coor(int B, int N, int D, int H, int W, const float *xs,
  * float32 grid tensors, :74-89).  Outputs must hold B*N*D*H*W int32 each; the
  * first counts[0] (points kept) / counts[1] (intervals) entries are valid,
  * counts is DEVICE int[2].  Order inside an interval is ascending ranks_depth
- * (the reference's unstable argsort leaves it unspecified).  `plan` (optional,
+ * (the reference's unstable argsort leaves it unspecified).  A point with a
+ * non-finite coordinate (NaN, +-inf -- e.g. every point of a camera whose intrinsic
+ * or post_rots matrix is singular) is dropped, like a point outside the grid; the
+ * same holds for every veon_lss_prepare_cameras* entry.  `plan` (optional,
  * veon_bev_pool_plan_ints(B, voxels_per_batch) int32, 16-B aligned; needs
  * voxels_per_batch % 64 == 0) receives the fused pool kernels' plan for free.
  * workspace: veon_lss_prepare_workspace_bytes(B*N*D*H*W, B*voxels_per_batch).

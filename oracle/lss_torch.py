@@ -76,6 +76,7 @@ def voxel_prepare(coor, lower, interval, gsize):
     P = B * N * D * H * W
     vox = ((coor - lower.to(coor)) / interval.to(coor)).long().view(P, 3)
     ok = ((vox >= 0) & (vox.float() < gsize.to(coor).view(1, 3))).all(1)
+    ok = ok & torch.isfinite(coor).all(-1).view(P)   # non-finite: dropped, explicitly
     idx = torch.nonzero(ok).squeeze(1)
     if idx.numel() == 0:
         return (None,) * 5

@@ -10,7 +10,7 @@ import torch
 
 from oracle import c_oracle
 from tests import helpers
-from veon_amd import _lib, conv3d_ops, synthetic
+from veon_amd import _lib, conv3d_ops, half, synthetic
 from veon_amd.ops.bev_pool_v2 import bev_pool as bp
 from veon_amd.ops.bev_pool_v2.bev_pool import bev_pool_v2
 
@@ -108,12 +108,13 @@ def test_rows_maxpool_random_structures_bit_exact(C, dtype):
         vs = bp.build_voxel_table(rb, st, B, Z * Y * X, attach=False)
         got = bp.rows_maxpool(dev(depth), feat_d, rd, rf, vs, shape, (2, 2, 2))
         assert np.array_equal(got.cpu().numpy(), want), rep
-        # padded bf16 channels-last output == bf16 rounding of the fp32 result
+        # padded half channels-last output (the process's flavour: bf16, or fp16 under
+        # VEON_HALF=fp16) == that type's rounding of the fp32 result
         vol = conv3d_ops.PaddedVolume(B, C, Z // 2, Y // 2, X // 2, DEV)
         vol.storage.fill_(7.0)          # interior must be overwritten everywhere
         bp.rows_maxpool(dev(depth), feat_d, rd, rf, vs, shape, (2, 2, 2), out_volume=vol)
         inner = vol.interior().permute(0, 4, 1, 2, 3).float().cpu().numpy()
-        assert np.array_equal(inner, torch.from_numpy(want).bfloat16().float().numpy())
+        assert np.array_equal(inner, torch.from_numpy(want).to(half.dtype()).float().numpy())
 
 
 def test_negative_sums_against_empty_neighbours():
@@ -171,7 +172,7 @@ def test_veon_shape_rows_bit_exact(dtype):
     bp.bev_pool_v2_maxpool(dev(depth), feat_d, rd, rf, rb, shape, st, ln, (2, 2, 2),
                            out_volume=vol)
     inner = vol.interior().permute(0, 4, 1, 2, 3).float().cpu().numpy()
-    assert np.array_equal(inner, torch.from_numpy(want_mp).bfloat16().float().numpy())
+    assert np.array_equal(inner, torch.from_numpy(want_mp).to(half.dtype()).float().numpy())
     # the halo stayed zero
     assert float(vol.rows.float().abs().sum()) == pytest.approx(
         float(np.abs(inner.astype(np.float64)).sum()), rel=1e-3)

@@ -213,14 +213,18 @@ __global__ __launch_bounds__(kBlock) void k_lidar_coor(
 }
 
 // view_transformer_raw.py:267-286: voxel, filter, float32 rank.  key = -1 when
-// the point is dropped.
+// the point is dropped.  A NaN coordinate drops the point explicitly: the float ->
+// int64 conversion of NaN is not defined (this target gives 0, i.e. voxel 0 of that
+// axis, x86 gives INT64_MIN); +-inf and huge values convert out of range and fail the
+// range test below.
 __device__ __forceinline__ int voxel_key(const GridF& gr, const float* c,
                                          int64_t ib) {
   const float fx = (c[0] - gr.lo[0]) / gr.step[0];
   const float fy = (c[1] - gr.lo[1]) / gr.step[1];
   const float fz = (c[2] - gr.lo[2]) / gr.step[2];
   const long long ix = (long long)fx, iy = (long long)fy, iz = (long long)fz;
-  const bool ok = (ix >= 0) && ((float)ix < gr.size[0]) && (iy >= 0) &&
+  const bool ok = (fx == fx) && (fy == fy) && (fz == fz) && (ix >= 0) &&
+                  ((float)ix < gr.size[0]) && (iy >= 0) &&
                   ((float)iy < gr.size[1]) && (iz >= 0) &&
                   ((float)iz < gr.size[2]);
   if (!ok) return -1;

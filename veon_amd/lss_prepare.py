@@ -91,6 +91,9 @@ def voxel_pooling_prepare_v2_torch(coor, lower, interval, gsize):
     lower, interval, gsize = lower.to(coor), interval.to(coor), gsize.to(coor)
     vox = ((coor - lower) / interval).long().view(P, 3)        # trunc (:267-269)
     inside = ((vox >= 0) & (vox.float() < gsize.view(1, 3))).all(1)  # (:275-277)
+    # a point with a non-finite coordinate is dropped, stated explicitly: the
+    # float -> int64 conversion of NaN / inf is host-dependent (x86 gives INT64_MIN)
+    inside = inside & torch.isfinite(coor).all(-1).view(P)
     idx = torch.nonzero(inside).squeeze(1)
     if idx.numel() == 0:
         return None, None, None, None, None
