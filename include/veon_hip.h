@@ -645,8 +645,9 @@ int veon_vit_layernorm_padded(const float *x, const float *gamma, const float *b
                               void *stream);
 
 /* nn.LayerNorm over the last dim, fp32 in -> fp32 out, rows of d floats
- * (d % 128 == 0, d <= 1024): the token LayerNorms (ln_3 / ln_4 / pre_norm) of the
- * HSA network's blocks (highres_side_adaptor.py:108-135, 138-193). */
+ * (d % 128 == 0, d <= 1024; this entry point alone also d = 64): the token LayerNorms
+ * (ln_3 / ln_4 / pre_norm) of the HSA network's blocks (highres_side_adaptor.py:108-135,
+ * 138-193). */
 int veon_layernorm_f32(const float *x, const float *gamma, const float *beta,
                        float *out, int T, int d, float eps, void *stream);
 /* LayerNorm(x + offset) of (B, L, d) fp32 tokens, where offset is the nearest-neighbour
@@ -921,6 +922,57 @@ int veon_image_layernorm_bwd_bf16(const void *dout, int dout_tokens_f32,
                                   void *dx_padded, float *sums, void *workspace,
                                   int64_t workspace_bytes, int B, int C, int Y, int X,
                                   float eps, void *stream);
+
+/* ======== linear_train.hip ========================================================== */
+
+/*
+ * ---- training of the HSA FeedForward heads (LN -> Linear -> GELU -> Linear,
+ * highres_side_adaptor.py:55-66) and of the blocks' token LayerNorms on plain rows ----
+ * Rows are ordinary contiguous matrices WITHOUT guard rows; M (T) is any positive count.
+ *
+ * Weight gradient of a linear layer y = x W^T: dw[n][k] (fp32, the nn.Linear layout) =
+ * sum over the M rows of dy[row][n] * x[row][k], dy half [M][N], x half [M][K].  The
+ * kernel of veon_conv3d_k3_wgrad_bf16 as its one-tap case: one workgroup per tile and
+ * split of the rows, fp32 slabs of `workspace` (veon_linear_wgrad_workspace_bytes,
+ * host-only; -1 for an unsupported shape) added in index order: no atomics,
+ * bit-reproducible.  Rows >= M are never read (bounded buffer resources) and contribute
+ * exactly zero.  K % 64 == 0, N % 64 == 0 and M * max(K, N) < 2^30, otherwise
+ * VEON_ERR_BAD_ARG; a workspace that is too small gives VEON_ERR_WORKSPACE.
+ */
+int64_t veon_linear_wgrad_workspace_bytes(int M, int K, int N);
+int veon_linear_wgrad_bf16(const void *dy, const void *x, float *dw, void *workspace,
+                           int64_t workspace_bytes, int M, int K, int N, void *stream);
+
+/*
+ * The bias gradient: sums[N] (fp32) = sum over the M rows of dy half [M][N].  Two stages
+ * in a fixed order, no atomics; `workspace`: veon_rows_colsum_workspace_bytes(N) bytes
+ * (host-only; -1: unsupported N).  N % 8 == 0.
+ */
+int64_t veon_rows_colsum_workspace_bytes(int N);
+int veon_rows_colsum_bf16(const void *dy, float *sums, void *workspace,
+                          int64_t workspace_bytes, int M, int N, void *stream);
+
+/*
+ * h = GELU(y) and dy = dh * GELU'(y), GELU'(y) = Phi(y) + y phi(y), elementwise on n half
+ * values (n % 8 == 0): the erf form in fp32 from the stored half value, both from one
+ * erfc evaluation, as veon_image_layernorm_bwd_bf16's gelu_in.  Outputs must not alias
+ * inputs.
+ */
+int veon_gelu_bf16(const void *y, void *h, int64_t n, void *stream);
+int veon_gelu_bwd_bf16(const void *dh, const void *y, void *dy, int64_t n, void *stream);
+
+/*
+ * Backward of nn.LayerNorm over the last axis at its stored fp32 input x [T][d]; the row
+ * statistics are recomputed.  `dout`: fp32 [T][d] (dout_half == 0) or half [T][d].
+ * dx fp32 [T][d]; sums[2][d] (fp32): [0] dgamma = sum dout * xhat, [1] dbeta = sum dout.
+ * Two stages in a fixed order, no atomics; `workspace`:
+ * veon_layernorm_f32_bwd_workspace_bytes(d) bytes (host-only; -1: unsupported d).
+ * d % 64 == 0, d <= 1024.  dx must not alias an input.
+ */
+int64_t veon_layernorm_f32_bwd_workspace_bytes(int d);
+int veon_layernorm_f32_bwd(const void *dout, int dout_half, const float *x,
+                           const float *gamma, float *dx, float *sums, void *workspace,
+                           int64_t workspace_bytes, int T, int d, float eps, void *stream);
 
 /* ======== occ_head.hip ============================================================== */
 

@@ -1,15 +1,21 @@
 #!/usr/bin/env python
-"""Training step of the HSA network's ConvBlocks (forward + backward) at the VEON shape:
-6 cameras, 512 x 1408 images, 8 x 8 patches -> 64 x 176 tokens of 384 channels.  Two
-subjects, three structures each, in one process in alternating rounds:
+"""Training step of the HSA network (forward + backward) at the VEON shape: 6 cameras,
+512 x 1408 images, 8 x 8 patches -> 64 x 176 tokens of 384 channels.  Three subjects,
+three structures each, in one process in alternating rounds:
 
     block    one ConvBlock(384, 384) on 6 x (64 x 176) tokens with ``residual``
+    head     FeedForward(384, 384, 2304) on 6 x (64 x 176) tokens through
+             ``forward_resized`` to 16 x 44 (head_attn of the AttnManipulateBlock)
     network  HighresSideAdaptorNetwork.build() on 6 x 3 x 512 x 1408 (``--small``:
              256 x 704), random gradients seeded on ``attns`` and ``supp``
 
-    torch fp32      what a training step runs without the switch (nn.Conv2d / LayerNorm)
+    torch fp32      what a training step runs without the switches (nn.Conv2d / Linear /
+                    LayerNorm)
     torch autocast  the same modules under torch.autocast with the build's half dtype
-    native          ConvBlock.hip_train = True (csrc/conv2d_train.hip)
+    native          every ``hip_train`` switch on: ConvBlock (csrc/conv2d_train.hip),
+                    FeedForward and the blocks' token LayerNorms (csrc/linear_train.hip)
+
+``--subject wgrad`` times the linear weight gradient alone at the heads' two shapes.
 
     python tools/hsa_train_bench.py [--rounds 5] [--steps 5] [--quick] [--small]
                                     [--only native] [--subject block]
@@ -30,15 +36,22 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from veon_amd import half  # noqa: E402
 from veon_amd.models.semantic_net.hsa_network import (  # noqa: E402
-    ConvBlock, HighresSideAdaptorNetwork)
+    AttnManipulateBlock, ConvBlock, FeedForward, HighresSideAdaptorBlock,
+    HighresSideAdaptorNetwork)
 
 STRUCTURES = ('torch fp32', 'torch autocast', 'native')
-SUBJECTS = ('block', 'network')
+SUBJECTS = ('block', 'head', 'network')
+SWITCHED = (ConvBlock, FeedForward, HighresSideAdaptorBlock, AttnManipulateBlock)
+
+
+def _set_native(on):
+    for cls in SWITCHED:
+        cls.hip_train = on
 
 
 def _run(structure, forward, backward):
     def step():
-        ConvBlock.hip_train = structure == 'native'
+        _set_native(structure == 'native')
         try:
             if structure == 'torch autocast':
                 with torch.autocast('cuda', dtype=half.dtype()):
@@ -47,7 +60,7 @@ def _run(structure, forward, backward):
                 out = forward()
             return backward(out)
         finally:
-            ConvBlock.hip_train = False
+            _set_native(False)
     return step
 
 
@@ -67,6 +80,41 @@ def block_subject(dev, gen):
         return state['x'].grad
     return 'ConvBlock(384, 384), training mode, 6 x (64 x 176) tokens + residual', \
         forward, backward, blk
+
+
+def head_subject(dev, gen):
+    ff = FeedForward(384, 384, 2304).to(dev).train()
+    x = torch.randn(6, 64 * 176, 384, generator=gen).to(dev)
+    gout = torch.randn(6, 2304, 16, 44, generator=gen).to(dev)
+    state = {}
+
+    def forward():
+        state['x'] = x.detach().requires_grad_()
+        return ff.forward_resized(state['x'], (64, 176), (16, 44))
+
+    def backward(out):
+        ff.zero_grad(set_to_none=True)
+        out.backward(gout.to(out.dtype))
+        return state['x'].grad
+    return 'FeedForward(384, 384, 2304), training mode, 6 x (64 x 176) tokens, ' \
+        'forward_resized to 16 x 44', forward, backward, ff
+
+
+def wgrad_times(dev, gen, iters=20):
+    """The linear weight gradient alone (kernel + reduce, device events over ``iters``
+    back-to-back calls after two warm-ups) and its share of the 2.5 PFLOP/s bf16 peak."""
+    from veon_amd import vit_ops
+    print('linear weight gradient, %d calls back to back' % iters)
+    for M, K, N in ((67584, 384, 384), (4224, 384, 2304)):
+        dy = torch.randn(M, N, generator=gen).to(half.dtype()).to(dev)
+        x = torch.randn(M, K, generator=gen).to(half.dtype()).to(dev)
+        out = torch.empty(N, K, device=dev)
+        for _ in range(2):
+            vit_ops.linear_wgrad(dy, x, out)
+        ms = sorted(timed(lambda: vit_ops.linear_wgrad(dy, x, out), iters) for _ in range(5))
+        tflops = 2.0 * M * K * N / (ms[2] * 1e-3) / 1e12
+        print('(M, K, N) = (%6d, %4d, %4d) | %8.4f ms median [%8.4f .. %8.4f] | %7.1f TFLOP/s'
+              ' | %5.1f %% of peak' % (M, K, N, ms[2], ms[0], ms[-1], tflops, tflops / 25.0))
 
 
 def network_subject(dev, gen, small):
@@ -148,7 +196,7 @@ def main():
     ap.add_argument('--quick', action='store_true', help='2 rounds of 2 steps (profiler run)')
     ap.add_argument('--small', action='store_true', help='network on 256 x 704 images')
     ap.add_argument('--only', choices=STRUCTURES, default=None)
-    ap.add_argument('--subject', choices=SUBJECTS, default=None)
+    ap.add_argument('--subject', choices=SUBJECTS + ('wgrad',), default=None)
     a = ap.parse_args()
     rounds, steps = (2, 2) if a.quick else (a.rounds, a.steps)
     if not torch.cuda.is_available():
@@ -160,8 +208,13 @@ def main():
     print('device %s; %s operands; %d rounds of %d steps, structures alternating' % (
         torch.cuda.get_device_name(0), half.name(), rounds, steps))
     for subject in ([a.subject] if a.subject else SUBJECTS):
+        if subject == 'wgrad':
+            wgrad_times(dev, gen)
+            continue
         if subject == 'block':
             title, forward, backward, keep = block_subject(dev, gen)
+        elif subject == 'head':
+            title, forward, backward, keep = head_subject(dev, gen)
         else:
             title, forward, backward, keep = network_subject(dev, gen, a.small)
         measure(title, forward, backward, names, rounds, steps)

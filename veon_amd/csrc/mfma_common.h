@@ -91,6 +91,11 @@ __device__ __forceinline__ rsrc_t make_rsrc(const void* base) {
   // no bounds (0xffffffff records), DATA_FORMAT = 32-bit (gfx9 family dword 3)
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0xffffffff, 0x00020000);
 }
+// `bytes` records from base: a lane whose vector offset (+ the instruction's immediate)
+// is not below it reads nothing.  The scalar offset takes no part in that check.
+__device__ __forceinline__ rsrc_t make_rsrc_bounded(const void* base, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
+}
 __device__ __forceinline__ void buffer_load_lds16(rsrc_t r, lptr_t dst, int voffset,
                                                   int soffset) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voffset, soffset, 0, 0);
@@ -98,6 +103,7 @@ __device__ __forceinline__ void buffer_load_lds16(rsrc_t r, lptr_t dst, int voff
 #else
 typedef int rsrc_t;
 __device__ inline rsrc_t make_rsrc(const void*) { return 0; }
+__device__ inline rsrc_t make_rsrc_bounded(const void*, unsigned) { return 0; }
 __device__ inline void buffer_load_lds16(rsrc_t, lptr_t, int, int) {}
 #endif
 

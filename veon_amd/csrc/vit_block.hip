@@ -1257,14 +1257,50 @@ __global__ __launch_bounds__(256) void k_layernorm_f32(
     }
   }
 }
+
+// The same LayerNorm at d = 64 (the narrowest HSA width): a quarter of a wave per row, one
+// float4 per lane; plain rows only.
+__global__ __launch_bounds__(256) void k_layernorm_f32_d64(
+    const float* __restrict__ x, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ out, int T, float eps) {
+  const int l = threadIdx.x & 15;
+  const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (row >= T) return;  // a whole quarter-wave leaves; the shuffles stay inside one
+  const float4 v = reinterpret_cast<const float4*>(x + row * 64)[l];
+  float s = (v.x + v.y) + (v.z + v.w);
+#pragma unroll
+  for (int d = 8; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+  const float mean = s / 64;
+  const float a = v.x - mean, b = v.y - mean, c = v.z - mean, e = v.w - mean;
+  float sq = (a * a + b * b) + (c * c + e * e);
+#pragma unroll
+  for (int d = 8; d >= 1; d >>= 1) sq += __shfl_xor(sq, d);
+  const float rstd = rsqrtf(sq / 64 + eps);
+  const float4 g = reinterpret_cast<const float4*>(gamma)[l];
+  const float4 bt = reinterpret_cast<const float4*>(beta)[l];
+  float4 r;
+  r.x = a * rstd * g.x + bt.x;
+  r.y = b * rstd * g.y + bt.y;
+  r.z = c * rstd * g.z + bt.z;
+  r.w = e * rstd * g.w + bt.w;
+  reinterpret_cast<float4*>(out + row * 64)[l] = r;
+}
 }  // namespace
 
 static int layernorm_f32_impl(const float* x, const float* gamma, const float* beta,
                               void* out, int T, int d, float eps, int Y, int X,
                               bool padded, void* stream, LnAdd ad = LnAdd{}) {
-  if (!x || !gamma || !beta || !out || T <= 0 || d <= 0 || d % 128 != 0 || d > 1024)
+  const bool narrow = d == 64 && !padded && ad.add == nullptr;
+  if (!x || !gamma || !beta || !out || T <= 0 || d <= 0 || (d % 128 != 0 && !narrow) ||
+      d > 1024)
     return VEON_ERR_BAD_ARG;
   if (!al16(x) || !al16(gamma) || !al16(beta) || !al16(out)) return VEON_ERR_BAD_ARG;
+  if (narrow) {
+    hipLaunchKernelGGL(k_layernorm_f32_d64, dim3((unsigned)((T + 15) / 16)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), x, gamma, beta,
+                       static_cast<float*>(out), T, eps);
+    return launch_status();
+  }
   if (padded && (Y <= 0 || X <= 0 || T % ((int64_t)Y * X) != 0)) return VEON_ERR_BAD_ARG;
   const dim3 grid((unsigned)((T + 7) / 8));
   hipStream_t s = static_cast<hipStream_t>(stream);

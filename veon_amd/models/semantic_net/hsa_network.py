@@ -30,9 +30,43 @@ from ... import half as _half
 from .resize import interpolate as _interp
 
 
-def _ln(mod, x, native):
+class _TokenLayerNormFn(torch.autograd.Function):
+    """nn.LayerNorm of fp32 tokens for training: forward on ``veon_layernorm_f32``,
+    backward on ``veon_layernorm_f32_bwd`` (statistics recomputed from the saved input)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        ctx.eps = eps
+        ctx.save_for_backward(x, gamma)
+        return vit_ops.layernorm_f32(x, gamma.detach(), beta.detach(), eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        x, gamma = ctx.saved_tensors
+        dx, dg, db = vit_ops.layernorm_f32_bwd(dout.contiguous(), x, gamma.detach(), ctx.eps)
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None, dg if need[1] else None, db if need[2] else None,
+                None)
+
+
+def _ln_train_ok(mod, x):
+    """A token LayerNorm the training kernels take: affine, fp32, over a last axis of 64 or
+    a multiple of 128 up to 1024 (what the fp32 forward kernel takes) on ROCm fp32 tokens."""
+    d = x.shape[-1]
+    return (isinstance(mod, nn.LayerNorm) and x.is_cuda and x.dtype == torch.float32
+            and len(mod.normalized_shape) == 1 and (d % 128 == 0 or d == 64) and d <= 1024
+            and mod.weight is not None and mod.bias is not None
+            and mod.weight.dtype == torch.float32)
+
+
+def _ln(mod, x, native, train=False):
     """``mod(x)`` for the token LayerNorms of the blocks; with ``native`` (the
-    block runs its ConvBlock on the MFMA path) on the fp32 LayerNorm kernel."""
+    block runs its ConvBlock on the MFMA path) on the fp32 LayerNorm kernel; with
+    ``train`` (the block's ``hip_train``, in training mode under autograd) through
+    ``_TokenLayerNormFn``.  An nn.Identity or a width the kernels do not take: ``mod(x)``."""
+    if train and _ln_train_ok(mod, x):
+        return _TokenLayerNormFn.apply(x.contiguous(), mod.weight, mod.bias, mod.eps)
     if (native and isinstance(mod, nn.LayerNorm) and x.is_cuda
             and not torch.is_grad_enabled() and x.dtype == torch.float32
             and x.shape[-1] % 128 == 0 and x.shape[-1] <= 1024
@@ -42,8 +76,81 @@ def _ln(mod, x, native):
     return mod(x)
 
 
+def _half_weight(w, transpose=False):
+    """The half copy of an fp32 Linear weight, re-packed every step; ``transpose``:
+    [K][N], the weight of the data gradient as a GEMM of ``vit_ops.linear``."""
+    w = w.detach().float()
+    return vit_ops.to_bf16(w.t().contiguous() if transpose else w)
+
+
+class _FFHiddenFn(torch.autograd.Function):
+    """The first half of ``FeedForward`` for training (csrc/linear_train.hip): fp32 tokens
+    x -> h = GELU(LN(x) W1^T + b1), half.  Saved for backward: x, the half rows LN(x) and the
+    pre-activation y1 (GELU is not invertible).  Parameter gradients are fp32 in the
+    parameters' own layout.  In the fp16 flavour every gradient between two kernels is
+    rounded to fp16: loss scaling is the caller's business."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, w1, b1, eps):
+        x2 = x.detach().contiguous().view(-1, x.shape[-1])
+        xn = vit_ops.layernorm(x2, gamma.detach(), beta.detach(), eps)
+        y1 = vit_ops.linear(xn, _half_weight(w1), b1.detach().float().contiguous())
+        ctx.eps = eps
+        ctx.save_for_backward(x2, xn, y1, gamma, w1)
+        return vit_ops.gelu(y1).view(*x.shape[:-1], -1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh):
+        x2, xn, y1, gamma, w1 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy1 = vit_ops.gelu_bwd(dh.contiguous().view(y1.shape), y1)
+        db1 = vit_ops.colsum(dy1).to(w1.dtype) if need[4] else None
+        dw1 = vit_ops.linear_wgrad(dy1, xn).to(w1.dtype) if need[3] else None
+        dx = dg = de = None
+        if need[0] or need[1] or need[2]:
+            dxn = vit_ops.linear(dy1, _half_weight(w1, transpose=True))
+            dx, dg, de = vit_ops.layernorm_f32_bwd(dxn, x2, gamma.detach().contiguous(),
+                                                   ctx.eps)
+            dx = dx.view(*dh.shape[:-1], -1) if need[0] else None
+        return dx, dg, de, dw1, db1, None
+
+
+class _LinearTrainFn(torch.autograd.Function):
+    """nn.Linear on half rows for training: a [.., K] half -> a W^T + b, half; backward:
+    bias gradient (column sum), weight gradient (``vit_ops.linear_wgrad``) and the data
+    gradient as a GEMM on the transposed weight.  Gradients as in ``_FFHiddenFn``."""
+
+    @staticmethod
+    def forward(ctx, a, w, b):
+        ctx.save_for_backward(a, w)
+        return vit_ops.linear(a, _half_weight(w), b.detach().float().contiguous())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        a, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy = dy.contiguous()
+        db = vit_ops.colsum(dy).to(w.dtype) if need[2] else None
+        dw = vit_ops.linear_wgrad(dy, a).to(w.dtype) if need[1] else None
+        da = vit_ops.linear(dy, _half_weight(w, transpose=True)) if need[0] else None
+        return da, dw, db
+
+
 class FeedForward(NativeCacheMixin, nn.Module):
+    """LN -> Linear -> GELU -> Linear on tokens (:55-66).
+
+    ``hip_train`` (class attribute, default False): opt-in native TRAINING path.  When
+    set, a training-mode head under autograd on ROCm fp32 tokens whose widths the kernels
+    take runs ``_FFHiddenFn`` and ``_LinearTrainFn`` (MFMA GEMMs, linear weight gradient,
+    LayerNorm and GELU backwards in HIP); ``forward_resized`` then resizes the half hidden
+    map (torch, under autograd) and runs the wide Linear on the surviving tokens, as the
+    inference path does.  Anything else takes the code below unchanged.  It does not
+    depend on ``conv_dtype``."""
+
     _native_cache = ('_hip',)
+    hip_train = False
 
     def __init__(self, dim, hidden_dim, out_dim=-1):
         super().__init__()
@@ -73,10 +180,38 @@ class FeedForward(NativeCacheMixin, nn.Module):
                               ln.bias.detach(), ln.eps)
         return vit_ops.linear(h, w1, b1, vit_ops.EPI_GELU), w2, b2
 
+    def _hip_train_ok(self, x):
+        """The native training path's own test: the switch, training mode under autograd,
+        ROCm fp32 tokens, the three widths multiples of 64 (the weight gradient's tiles)
+        and the LayerNorm's at most 1024, an affine LayerNorm, both Linears with bias,
+        exact GELU, fp32 parameters."""
+        if not (self.hip_train and self.training and torch.is_grad_enabled()
+                and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+                and x.dim() >= 2 and len(self.net) == 4):
+            return False
+        ln, fc1, act, fc2 = self.net
+        return (isinstance(ln, nn.LayerNorm) and len(ln.normalized_shape) == 1
+                and ln.weight is not None and ln.bias is not None
+                and ln.weight.dtype == torch.float32
+                and all(isinstance(fc, nn.Linear) and fc.bias is not None
+                        and fc.weight.dtype == torch.float32 for fc in (fc1, fc2))
+                and all(d % 64 == 0 for d in (fc1.in_features, fc1.out_features,
+                                              fc2.out_features))
+                and fc1.in_features <= 1024 and x.shape[-1] == fc1.in_features
+                and isinstance(act, nn.GELU)
+                and getattr(act, 'approximate', 'none') == 'none')
+
+    def _train_hidden(self, x):
+        ln, fc1, _, _ = self.net
+        return _FFHiddenFn.apply(x, ln.weight, ln.bias, fc1.weight, fc1.bias, ln.eps)
+
     def forward(self, x):
         if self._hip_ok(x):
             h, w2, b2 = self._hip_hidden(x)
             return vit_ops.linear(h, w2, b2).float().view(*x.shape[:-1], -1)
+        if self._hip_train_ok(x):
+            fc2 = self.net[3]
+            return _LinearTrainFn.apply(self._train_hidden(x), fc2.weight, fc2.bias).float()
         return self.net(x)
 
     def forward_resized(self, x, side_shape, new_shape):
@@ -90,6 +225,13 @@ class FeedForward(NativeCacheMixin, nn.Module):
         B = x.shape[0]
         H, W = side_shape
         h, w = new_shape
+        if not self._hip_ok(x) and self._hip_train_ok(x):
+            fc2 = self.net[3]
+            hid = self._train_hidden(x).view(B, H, W, -1).permute(0, 3, 1, 2)
+            hid = F.interpolate(hid, size=(h, w), mode='bilinear')   # torch, under autograd
+            rows = hid.permute(0, 2, 3, 1).reshape(B * h * w, -1).contiguous()
+            y = _LinearTrainFn.apply(rows, fc2.weight, fc2.bias)     # (B*h*w, out) half
+            return y.view(B, h * w, -1).permute(0, 2, 1).float().contiguous().view(B, -1, h, w)
         if not self._hip_ok(x):
             y = self(x).permute(0, 2, 1).reshape(B, -1, H, W)
             return _interp(y, size=(h, w), mode='bilinear').contiguous()
@@ -294,7 +436,14 @@ class ConvBlock(NativeCacheMixin, nn.Module):
 
 class HighresSideAdaptorBlock(nn.Module):
     """:108-135 -- x += ConvBlock(ln_3(x)); the last tokens += the (projected,
-    nearest-resized) CLIP feature map; ln_4."""
+    nearest-resized) CLIP feature map; ln_4.
+
+    ``hip_train`` (class attribute, default False): in training mode under autograd the
+    token LayerNorms (pre_norm, ln_3, ln_4) run through ``_TokenLayerNormFn``; ln_3 is
+    then applied here instead of being handed to the ConvBlock as ``pre_ln``.  The offset
+    add in front of ln_4 stays the torch ``cat``."""
+
+    hip_train = False
 
     def __init__(self, dim, mlp_dim=960, neck_dim=0, pre_norm=False, use_add=False,
                  use_checkpoint=False):
@@ -311,8 +460,12 @@ class HighresSideAdaptorBlock(nn.Module):
     def forward(self, x, x_pos, ext, ext_pos, offset=None, offset_shape=(1, 1)):
         B, C_clip, h_ext, w_ext = ext.shape
         native = self.ff.conv_dtype == _half.dtype() and not self.training
-        x = _ln(self.pre_norm, x, native)
-        x = self.ff(x, offset_shape, residual=x, pre_ln=self.ln_3)
+        train = self.hip_train and self.training and torch.is_grad_enabled()
+        x = _ln(self.pre_norm, x, native, train)
+        if train:
+            x = self.ff(_ln(self.ln_3, x, False, True), offset_shape, residual=x)
+        else:
+            x = self.ff(x, offset_shape, residual=x, pre_ln=self.ln_3)
         if offset is not None:
             offset = self.neck_add(offset.reshape(B, C_clip, -1).permute(0, 2, 1))
             if (native and x.is_cuda and not torch.is_grad_enabled()
@@ -328,13 +481,18 @@ class HighresSideAdaptorBlock(nn.Module):
                              size=offset_shape)
             offset = offset.reshape(B, offset.shape[1], -1).permute(0, 2, 1)
             x = torch.cat([x[:, :-offset.shape[1]], x[:, -offset.shape[1]:] + offset], 1)
-        return _ln(self.ln_4, x, native)
+        return _ln(self.ln_4, x, native, train)
 
 
 class AttnManipulateBlock(nn.Module):
     """:138-193 -- ConvBlock, then two token-wise heads: per-layer / per-head
     embeddings whose Gram matrices are CLIP's dense attention biases
-    (layers, B, heads, hw, hw), and the "supp" feature map for the lift."""
+    (layers, B, heads, hw, hw), and the "supp" feature map for the lift.
+
+    ``hip_train`` (class attribute, default False): as ``HighresSideAdaptorBlock``'s, for
+    pre_norm, ln_3 and ln_4.  The heads have their own switch (``FeedForward``)."""
+
+    hip_train = False
 
     def __init__(self, dim, mlp_dim=768, clip_dim=1024, heads=16, dim_head=64,
                  attn_layers=6, add_layers=2, supp_dim=384, pre_norm=False,
@@ -358,8 +516,13 @@ class AttnManipulateBlock(nn.Module):
 
     def forward(self, x, side_shape=(1, 1), new_shape=(1, 1)):
         native = self.ff.conv_dtype == _half.dtype() and not self.training
-        x = _ln(self.pre_norm, x, native)
-        x = _ln(self.ln_4, self.ff(x, side_shape, pre_ln=self.ln_3), native)
+        train = self.hip_train and self.training and torch.is_grad_enabled()
+        x = _ln(self.pre_norm, x, native, train)
+        if train:
+            x = self.ff(_ln(self.ln_3, x, False, True), side_shape)
+        else:
+            x = self.ff(x, side_shape, pre_ln=self.ln_3)
+        x = _ln(self.ln_4, x, native, train)
         supp = self.head_supp(x)
         H, W = side_shape
         h, w = new_shape

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from . import half as _half
+from .conv3d_ops import _workspace
 
 EPI_BF16, EPI_GELU, EPI_QUICKGELU, EPI_RESID = 0, 1, 2, 3
 EPI_AFFINE, EPI_AFFINE_RELU = 4, 5
@@ -70,7 +71,7 @@ def layernorm_padded(x, weight, bias, d, eps=1e-6):
 
 def layernorm_f32(x, weight, bias, eps=1e-5):
     """x fp32 [..., d] -> fp32 [..., d] (nn.LayerNorm over the last dim);
-    d % 128 == 0, d <= 1024."""
+    d % 128 == 0 or d == 64, d <= 1024."""
     dev = _dev(x, weight, bias)
     d = x.shape[-1]
     assert x.dtype == torch.float32 and x.is_contiguous()
@@ -121,6 +122,99 @@ def linear_residual_(resid, a, w, bias=None, gamma=None):
     assert resid.numel() == M * N
     _lib.launch('veon_vit_gemm', dev, a, w, bias, gamma, resid, None, M, N, K, EPI_RESID)
     return resid
+
+
+# ------------------------------------------------- training passes (csrc/linear_train.hip)
+def _rows(t):
+    """(M, width) of a contiguous half tensor read as rows of its last axis."""
+    _lib.require_half(t)
+    assert t.is_contiguous()
+    return t.numel() // t.shape[-1], t.shape[-1]
+
+
+def linear_wgrad_workspace_bytes(M, K, N):
+    """Bytes of split-K slabs ``linear_wgrad`` needs (host-only); -1: unsupported."""
+    return int(_lib.lib().veon_linear_wgrad_workspace_bytes(M, K, N))
+
+
+def linear_wgrad(dy, x, out=None):
+    """Weight gradient of ``y = x W^T``: dy half [M, N], x half [M, K] -> fp32 [N, K] (the
+    nn.Linear layout) = dy^T x, the contraction over the M rows in fp32.  K and N
+    multiples of 64.  Deterministic: split-K slabs added in a fixed order.  In the fp16
+    flavour the operands are fp16 gradients as they are: loss scaling is the caller's."""
+    dev = _dev(dy, x)
+    (M, N), (Mx, K) = _rows(dy), _rows(x)
+    assert M == Mx
+    nbytes = linear_wgrad_workspace_bytes(M, K, N)
+    if nbytes < 0:
+        raise _lib.VeonHipError('linear_wgrad: unsupported shape %d rows, %d -> %d' % (M, K, N))
+    ws = _workspace('linear_wgrad', nbytes, dev, M, K, N)
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float32, device=dev)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == (N, K)
+    _lib.launch('veon_linear_wgrad_bf16', dev, dy, x, out, ws, nbytes, M, K, N)
+    return out
+
+
+def linear_wgrad_ref(dy, x):
+    """``linear_wgrad`` in torch, in the operands' own dtype (pass fp64 for a reference)."""
+    return dy.reshape(-1, dy.shape[-1]).t() @ x.reshape(-1, x.shape[-1])
+
+
+def colsum(dy):
+    """dy half [M, N] -> fp32 [N], the sum over the rows (a bias gradient).  Two stages
+    in a fixed order: deterministic."""
+    dev = _dev(dy)
+    M, N = _rows(dy)
+    nbytes = int(_lib.lib().veon_rows_colsum_workspace_bytes(N))
+    if nbytes < 0:
+        raise _lib.VeonHipError('colsum: unsupported width %d' % N)
+    ws = _workspace('colsum', nbytes, dev, N)
+    out = torch.empty(N, dtype=torch.float32, device=dev)
+    _lib.launch('veon_rows_colsum_bf16', dev, dy, out, ws, nbytes, M, N)
+    return out
+
+
+def gelu(y):
+    """GELU (erf form) of a half tensor, in fp32 from the stored half value -> half."""
+    dev = _dev(y)
+    _rows(y)
+    out = torch.empty_like(y)
+    _lib.launch('veon_gelu_bf16', dev, y, out, y.numel())
+    return out
+
+
+def gelu_bwd(dh, y):
+    """dh * GELU'(y), GELU'(y) = Phi(y) + y phi(y), on half tensors -> half."""
+    dev = _dev(dh, y)
+    _rows(y)
+    _rows(dh)
+    assert dh.shape == y.shape
+    out = torch.empty_like(y)
+    _lib.launch('veon_gelu_bwd_bf16', dev, dh, y, out, y.numel())
+    return out
+
+
+def layernorm_f32_bwd(dout, x, gamma, eps):
+    """Backward of nn.LayerNorm over the last axis at its stored fp32 input ``x``
+    [..., d]; ``dout`` fp32 or half, same shape.  -> (dx fp32, dgamma, dbeta fp32 [d]).
+    d % 64 == 0, d <= 1024."""
+    dev = _dev(dout, x, gamma)
+    d = x.shape[-1]
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    assert dout.shape == x.shape and dout.is_contiguous()
+    if dout.dtype != torch.float32:
+        _lib.require_half(dout)
+    assert gamma.dtype == torch.float32 and gamma.numel() == d and gamma.is_contiguous()
+    nbytes = int(_lib.lib().veon_layernorm_f32_bwd_workspace_bytes(d))
+    if nbytes < 0:
+        raise _lib.VeonHipError('layernorm_f32_bwd: unsupported width %d' % d)
+    ws = _workspace('lnf32bwd', nbytes, dev, d)
+    dx = torch.empty_like(x)
+    sums = torch.empty((2, d), dtype=torch.float32, device=dev)
+    _lib.launch('veon_layernorm_f32_bwd', dev, dout, 0 if dout.dtype == torch.float32 else 1,
+                x, gamma, dx, sums, ws, nbytes, x.numel() // d, d, float(eps))
+    return dx, sums[0], sums[1]
 
 
 LOG2E = 1.4426950408889634   # folded into q by the packers that set ``q_log2``
