@@ -974,6 +974,34 @@ int veon_layernorm_f32_bwd(const void *dout, int dout_half, const float *x,
                            const float *gamma, float *dx, float *sums, void *workspace,
                            int64_t workspace_bytes, int T, int d, float eps, void *stream);
 
+/* ======== attention_train.hip ======================================================= */
+
+/*
+ * Attention for training, head_dim 64, no additive bias.  qkv half [B][T][3][H][64] is
+ * the RAW output of the qkv Linear: the kernels multiply the scores by `scale`, so every
+ * gradient comes out in the parameters' own units.
+ *
+ * veon_vit_attention_fwd_lse: out half [B][T][H*64] = softmax(scale q k^T) v by the
+ * inference kernel, and lse[b][h][q] (fp32) = log2 sum_k exp2(scale log2(e) q.k), the
+ * log-sum-exp of the scaled scores in log2 units.  Rows of lse are
+ * veon_vit_attention_stats_len(T) floats (T rounded up to 64; 0: T <= 0), so lse holds
+ * B * H * stats_len floats; columns T.. of a row are not written.
+ *
+ * veon_vit_attention_bwd: dqkv half [B][T][3][H][64] from dout half [B][T][H*64] and the
+ * saved qkv, out and lse.  Three kernels: delta = rowsum(dout * out) into the workspace
+ * (veon_vit_attention_bwd_workspace_bytes(B, T, H) bytes, host-only; -1: bad shape), dq,
+ * and dk with dv.  Every element of dqkv is written; no atomics, no memset; columns T..
+ * of lse and of the workspace rows are never used.  dqkv must not alias an input.
+ */
+int64_t veon_vit_attention_stats_len(int T);
+int veon_vit_attention_fwd_lse(const void *qkv, void *out, float *lse, int B, int T, int H,
+                               int head_dim, float scale, void *stream);
+int64_t veon_vit_attention_bwd_workspace_bytes(int B, int T, int H);
+int veon_vit_attention_bwd(const void *qkv, const void *out, const void *dout,
+                           const float *lse, void *dqkv, void *workspace,
+                           int64_t workspace_bytes, int B, int T, int H, int head_dim,
+                           float scale, void *stream);
+
 /* ======== occ_head.hip ============================================================== */
 
 /* Tail of the occupancy path in one kernel (semantic_net/san_in_veon_temporal.py:

@@ -1,0 +1,182 @@
+"""Autograd functions of the native training paths of token models (the HSA heads, the
+DINOv2 blocks): each forward and backward is a sequence of HIP kernels of ``vit_ops``
+(csrc/vit_block.hip, linear_train.hip, attention_train.hip) on half rows.
+
+Conventions shared by all of them: activations between two kernels are half rows
+[M, width]; parameters stay fp32 ``nn.Parameter`` s and their half copies are re-packed
+every step; parameter gradients come back fp32 in the parameters' own layout, and only
+those ``needs_input_grad`` asks for are computed.  In the fp16 flavour every gradient
+between two kernels is rounded to fp16: loss scaling is the caller's business.
+"""
+import torch
+
+from .. import vit_ops
+
+LORA_PAD = 64   # the rank is zero-padded to the GEMM's and the weight gradient's tile width
+
+
+def _half_weight(w, transpose=False):
+    """The half copy of an fp32 Linear weight, re-packed every step; ``transpose``:
+    [K][N], the weight of the data gradient as a GEMM of ``vit_ops.linear``."""
+    w = w.detach().float()
+    return vit_ops.to_bf16(w.t().contiguous() if transpose else w)
+
+
+def _bias(b):
+    return None if b is None else b.detach().float().contiguous()
+
+
+def lora_pad_a(lora_a):
+    """lora_A fp32 [r, in] -> fp32 [64, in]: rows r.. zero."""
+    r, k = lora_a.shape
+    assert 0 < r <= LORA_PAD
+    out = lora_a.new_zeros((LORA_PAD, k), dtype=torch.float32)
+    out[:r] = lora_a.detach().float()
+    return out
+
+
+def lora_pad_b(lora_b, scaling):
+    """lora_B fp32 [out, r] -> fp32 [out, 64] = scaling * B in columns 0..r-1, zero beyond
+    (the scaling rides on B, so the branch is two plain GEMMs)."""
+    n, r = lora_b.shape
+    assert 0 < r <= LORA_PAD
+    out = lora_b.new_zeros((n, LORA_PAD), dtype=torch.float32)
+    out[:, :r] = lora_b.detach().float() * scaling
+    return out
+
+
+class _LNHalfFn(torch.autograd.Function):
+    """nn.LayerNorm of fp32 tokens [..., d] -> half rows [M, d]; backward on
+    ``veon_layernorm_f32_bwd`` from the half gradient (statistics recomputed from the
+    saved input)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        x2 = x.detach().contiguous().view(-1, x.shape[-1])
+        ctx.eps, ctx.shape = eps, x.shape
+        ctx.save_for_backward(x2, gamma)
+        return vit_ops.layernorm(x2, gamma.detach(), beta.detach(), eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dxn):
+        x2, gamma = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dg, de = vit_ops.layernorm_f32_bwd(dxn.contiguous(), x2,
+                                               gamma.detach().contiguous(), ctx.eps)
+        return (dx.view(ctx.shape) if need[0] else None, dg if need[1] else None,
+                de if need[2] else None, None)
+
+
+class _GeluFn(torch.autograd.Function):
+    """Exact GELU on half rows from the saved pre-activation."""
+
+    @staticmethod
+    def forward(ctx, y):
+        ctx.save_for_backward(y)
+        return vit_ops.gelu(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh):
+        y, = ctx.saved_tensors
+        return vit_ops.gelu_bwd(dh.contiguous(), y)
+
+
+class _FFHiddenFn(torch.autograd.Function):
+    """The first half of ``FeedForward`` for training (csrc/linear_train.hip): fp32 tokens
+    x -> h = GELU(LN(x) W1^T + b1), half.  Saved for backward: x, the half rows LN(x) and the
+    pre-activation y1 (GELU is not invertible).  Parameter gradients are fp32 in the
+    parameters' own layout.  In the fp16 flavour every gradient between two kernels is
+    rounded to fp16: loss scaling is the caller's business."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, w1, b1, eps):
+        x2 = x.detach().contiguous().view(-1, x.shape[-1])
+        xn = vit_ops.layernorm(x2, gamma.detach(), beta.detach(), eps)
+        y1 = vit_ops.linear(xn, _half_weight(w1), b1.detach().float().contiguous())
+        ctx.eps = eps
+        ctx.save_for_backward(x2, xn, y1, gamma, w1)
+        return vit_ops.gelu(y1).view(*x.shape[:-1], -1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh):
+        x2, xn, y1, gamma, w1 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy1 = vit_ops.gelu_bwd(dh.contiguous().view(y1.shape), y1)
+        db1 = vit_ops.colsum(dy1).to(w1.dtype) if need[4] else None
+        dw1 = vit_ops.linear_wgrad(dy1, xn).to(w1.dtype) if need[3] else None
+        dx = dg = de = None
+        if need[0] or need[1] or need[2]:
+            dxn = vit_ops.linear(dy1, _half_weight(w1, transpose=True))
+            dx, dg, de = vit_ops.layernorm_f32_bwd(dxn, x2, gamma.detach().contiguous(),
+                                                   ctx.eps)
+            dx = dx.view(*dh.shape[:-1], -1) if need[0] else None
+        return dx, dg, de, dw1, db1, None
+
+
+class _LinearTrainFn(torch.autograd.Function):
+    """nn.Linear on half rows for training: a [.., K] half -> a W^T + b, half (``b`` may be
+    None); backward: bias gradient (column sum), weight gradient (``vit_ops.linear_wgrad``)
+    and the data gradient as a GEMM on the transposed weight.  Gradients as in
+    ``_FFHiddenFn``."""
+
+    @staticmethod
+    def forward(ctx, a, w, b):
+        ctx.save_for_backward(a, w)
+        return vit_ops.linear(a, _half_weight(w), _bias(b))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        a, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy = dy.contiguous()
+        db = vit_ops.colsum(dy).to(w.dtype) if need[2] else None
+        dw = vit_ops.linear_wgrad(dy, a).to(w.dtype) if need[1] else None
+        da = vit_ops.linear(dy, _half_weight(w, transpose=True)) if need[0] else None
+        return da, dw, db
+
+
+class _LoRALinearTrainFn(torch.autograd.Function):
+    """An unmerged ``LoRALinear`` on half rows: y = a W^T + b + (a A^T)(s B)^T.  B A is NOT
+    merged into the half weight (B starts at zero and moves by the learning rate: a delta
+    below half an ulp of W would vanish from the forward); the low-rank branch runs as two
+    GEMMs of its own on the rank zero-padded to 64, u = a A_pad^T [M, 64] and u (s B)_pad^T,
+    added to the frozen product as half tensors.  Saved: a and u.  Backward: du = dy (s B)_pad
+    (a GEMM), d(sB)_pad = dy^T u and dA_pad = du^T a by ``vit_ops.linear_wgrad``; dA and dB
+    are their first r rows / columns.  The full-size weight gradient is computed only when
+    ``w`` asks for one (LoRA freezes it)."""
+
+    @staticmethod
+    def forward(ctx, a, w, b, lora_a, lora_b, scaling):
+        a_pad = vit_ops.to_bf16(lora_pad_a(lora_a))
+        b_pad = vit_ops.to_bf16(lora_pad_b(lora_b, scaling))
+        u = vit_ops.linear(a, a_pad)
+        y = vit_ops.linear(a, _half_weight(w), _bias(b)) + vit_ops.linear(u, b_pad)
+        ctx.scaling = scaling
+        ctx.save_for_backward(a, u, w, lora_a, lora_b)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        a, u, w, lora_a, lora_b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        r, s = lora_a.shape[0], ctx.scaling
+        dy = dy.contiguous()
+        db = vit_ops.colsum(dy).to(w.dtype) if need[2] else None
+        dw = vit_ops.linear_wgrad(dy, a).to(w.dtype) if need[1] else None
+        da = dla = dlb = None
+        if need[0] or need[3]:
+            # du = dy (s B)_pad: the GEMM's weight is (s B)_pad^T [64, out]
+            du = vit_ops.linear(dy, vit_ops.to_bf16(lora_pad_b(lora_b, s).t().contiguous()))
+            if need[3]:
+                dla = vit_ops.linear_wgrad(du, a)[:r].to(lora_a.dtype)
+            if need[0]:
+                da = vit_ops.linear(dy, _half_weight(w, transpose=True)) + vit_ops.linear(
+                    du, vit_ops.to_bf16(lora_pad_a(lora_a).t().contiguous()))
+        if need[4]:
+            dlb = (vit_ops.linear_wgrad(dy, u)[:, :r] * s).to(lora_b.dtype)
+        return da, dw, db, dla, dlb, None

@@ -23,6 +23,8 @@ import torch.nn.functional as F
 
 from ... import vit_ops
 from .._native_cache import NativeCacheMixin
+from .._train_fns import (LORA_PAD, _GeluFn, _LinearTrainFn, _LNHalfFn,
+                          _LoRALinearTrainFn)
 
 
 class LoRALinear(nn.Linear):
@@ -111,8 +113,46 @@ class LayerScale(nn.Module):
         return x * self.gamma
 
 
+def _train_linear_ok(lin):
+    """A Linear the native training step takes: a plain fp32 ``nn.Linear``, or an unmerged
+    ``LoRALinear`` of rank 0 < r <= 64 (r <= 0: a plain Linear under another class)."""
+    if type(lin) is nn.Linear:
+        ok = True
+    elif type(lin) is LoRALinear:
+        ok = lin.r <= 0 or (lin.r <= LORA_PAD and not lin.merged
+                            and lin.lora_A.dtype == torch.float32
+                            and lin.lora_B.dtype == torch.float32)
+    else:
+        return False
+    return (ok and lin.weight.dtype == torch.float32
+            and (lin.bias is None or lin.bias.dtype == torch.float32))
+
+
+def _train_linear(lin, a):
+    """``lin`` on half rows ``a`` [M, in] -> half [M, out] under autograd, on the kernels."""
+    if isinstance(lin, LoRALinear) and lin.r > 0:
+        return _LoRALinearTrainFn.apply(a, lin.weight, lin.bias, lin.lora_A, lin.lora_B,
+                                        lin.scaling)
+    return _LinearTrainFn.apply(a, lin.weight, lin.bias)
+
+
+def _ln_train_ok(ln, d):
+    return (type(ln) is nn.LayerNorm and tuple(ln.normalized_shape) == (d,)
+            and ln.weight is not None and ln.bias is not None
+            and ln.weight.dtype == torch.float32 and ln.bias.dtype == torch.float32)
+
+
 class Block(nn.Module):
-    """Pre-norm block: x += ls1(attn(norm1 x)); x += ls2(mlp(norm2 x))."""
+    """Pre-norm block: x += ls1(attn(norm1 x)); x += ls2(mlp(norm2 x)).
+
+    ``hip_train`` (class attribute, default False): opt-in native TRAINING path.  When set,
+    a training-mode block under autograd on ROCm fp32 tokens whose shapes the kernels take
+    (``_hip_train_ok``) runs LayerNorm, the four Linears (LoRA branches included), the
+    attention (csrc/attention_train.hip: no T x T tensor is saved) and GELU, forward and
+    backward, in HIP on half rows; the residual adds and LayerScale stay in torch on the
+    fp32 stream.  Anything else takes ``forward``'s two lines unchanged."""
+
+    hip_train = False
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=False,
                  proj_bias=True, ffn_bias=True, init_values=None, lora_r=-1):
@@ -124,7 +164,47 @@ class Block(nn.Module):
         self.mlp = Mlp(dim, int(dim * mlp_ratio), bias=ffn_bias, lora_r=lora_r)
         self.ls2 = LayerScale(dim, init_values) if init_values else nn.Identity()
 
+    def _hip_train_ok(self, x):
+        """The native training path's own test: the switch, training mode under autograd,
+        ROCm fp32 tokens [B, T, d], d % 64 == 0, head dim 64, d <= 1024 (the LayerNorm
+        backward), mlp_dim % 64 == 0, affine fp32 LayerNorms, exact GELU, fp32 parameters,
+        every Linear a plain nn.Linear or an unmerged LoRALinear with 0 < r <= 64."""
+        if not (self.hip_train and self.training and torch.is_grad_enabled()
+                and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 3 and type(self.attn) is Attention
+                and type(self.mlp) is Mlp):
+            return False
+        a, m, d = self.attn, self.mlp, x.shape[-1]
+        lins = (a.qkv, a.proj, m.fc1, m.fc2)
+        return (d % 64 == 0 and d <= 1024 and d == a.num_heads * 64
+                and a.qkv.in_features == d and a.qkv.out_features == 3 * d
+                and a.proj.in_features == d and a.proj.out_features == d
+                and m.fc1.in_features == d and m.fc1.out_features % 64 == 0
+                and m.fc2.in_features == m.fc1.out_features and m.fc2.out_features == d
+                and _ln_train_ok(self.norm1, d) and _ln_train_ok(self.norm2, d)
+                and type(m.act) is nn.GELU and getattr(m.act, 'approximate', 'none') == 'none'
+                and all(_train_linear_ok(lin) for lin in lins)
+                and all(type(ls) is nn.Identity
+                        or (type(ls) is LayerScale and ls.gamma.dtype == torch.float32)
+                        for ls in (self.ls1, self.ls2)))
+
+    def _hip_train_forward(self, x):
+        B, T, d = x.shape
+        a, m = self.attn, self.mlp
+        n1, n2 = self.norm1, self.norm2
+        xn = _LNHalfFn.apply(x, n1.weight, n1.bias, n1.eps)              # half [B*T, d]
+        qkv = _train_linear(a.qkv, xn).view(B, T, 3 * d)                 # raw q: no scale
+        o = vit_ops.attention_train(qkv, a.num_heads, a.scale)
+        y = _train_linear(a.proj, o.view(B * T, d))
+        x = x + self.ls1(y.view(B, T, d).float())
+        xn = _LNHalfFn.apply(x, n2.weight, n2.bias, n2.eps)
+        h = _GeluFn.apply(_train_linear(m.fc1, xn))
+        y = _train_linear(m.fc2, h)
+        return x + self.ls2(y.view(B, T, d).float())
+
     def forward(self, x):
+        if self._hip_train_ok(x):
+            return self._hip_train_forward(x)
         x = x + self.ls1(self.attn(self.norm1(x)))
         return x + self.ls2(self.mlp(self.norm2(x)))
 

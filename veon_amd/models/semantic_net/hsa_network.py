@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from ... import conv3d_ops, vit_ops
 from .._native_cache import NativeCacheMixin
+from .._train_fns import _FFHiddenFn, _LinearTrainFn
 from ... import half as _half
 
 
@@ -74,68 +75,6 @@ def _ln(mod, x, native, train=False):
         return vit_ops.layernorm_f32(x.contiguous(), mod.weight.detach(),
                                      mod.bias.detach(), mod.eps)
     return mod(x)
-
-
-def _half_weight(w, transpose=False):
-    """The half copy of an fp32 Linear weight, re-packed every step; ``transpose``:
-    [K][N], the weight of the data gradient as a GEMM of ``vit_ops.linear``."""
-    w = w.detach().float()
-    return vit_ops.to_bf16(w.t().contiguous() if transpose else w)
-
-
-class _FFHiddenFn(torch.autograd.Function):
-    """The first half of ``FeedForward`` for training (csrc/linear_train.hip): fp32 tokens
-    x -> h = GELU(LN(x) W1^T + b1), half.  Saved for backward: x, the half rows LN(x) and the
-    pre-activation y1 (GELU is not invertible).  Parameter gradients are fp32 in the
-    parameters' own layout.  In the fp16 flavour every gradient between two kernels is
-    rounded to fp16: loss scaling is the caller's business."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, w1, b1, eps):
-        x2 = x.detach().contiguous().view(-1, x.shape[-1])
-        xn = vit_ops.layernorm(x2, gamma.detach(), beta.detach(), eps)
-        y1 = vit_ops.linear(xn, _half_weight(w1), b1.detach().float().contiguous())
-        ctx.eps = eps
-        ctx.save_for_backward(x2, xn, y1, gamma, w1)
-        return vit_ops.gelu(y1).view(*x.shape[:-1], -1)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dh):
-        x2, xn, y1, gamma, w1 = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        dy1 = vit_ops.gelu_bwd(dh.contiguous().view(y1.shape), y1)
-        db1 = vit_ops.colsum(dy1).to(w1.dtype) if need[4] else None
-        dw1 = vit_ops.linear_wgrad(dy1, xn).to(w1.dtype) if need[3] else None
-        dx = dg = de = None
-        if need[0] or need[1] or need[2]:
-            dxn = vit_ops.linear(dy1, _half_weight(w1, transpose=True))
-            dx, dg, de = vit_ops.layernorm_f32_bwd(dxn, x2, gamma.detach().contiguous(),
-                                                   ctx.eps)
-            dx = dx.view(*dh.shape[:-1], -1) if need[0] else None
-        return dx, dg, de, dw1, db1, None
-
-
-class _LinearTrainFn(torch.autograd.Function):
-    """nn.Linear on half rows for training: a [.., K] half -> a W^T + b, half; backward:
-    bias gradient (column sum), weight gradient (``vit_ops.linear_wgrad``) and the data
-    gradient as a GEMM on the transposed weight.  Gradients as in ``_FFHiddenFn``."""
-
-    @staticmethod
-    def forward(ctx, a, w, b):
-        ctx.save_for_backward(a, w)
-        return vit_ops.linear(a, _half_weight(w), b.detach().float().contiguous())
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        a, w = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        dy = dy.contiguous()
-        db = vit_ops.colsum(dy).to(w.dtype) if need[2] else None
-        dw = vit_ops.linear_wgrad(dy, a).to(w.dtype) if need[1] else None
-        da = vit_ops.linear(dy, _half_weight(w, transpose=True)) if need[0] else None
-        return da, dw, db
 
 
 class FeedForward(NativeCacheMixin, nn.Module):

@@ -247,6 +247,116 @@ def attention(qkv, num_heads, bias=None, out=None, q_log2=False):
     return out
 
 
+# ------------------------------------------- attention for training (csrc/attention_train.hip)
+def attention_stats_len(T):
+    """Floats per (b, h) row of ``lse`` and of the backward's workspace: T rounded up to 64."""
+    return int(_lib.lib().veon_vit_attention_stats_len(int(T)))
+
+
+def _qkv_dims(qkv, num_heads):
+    _lib.require_half(qkv)
+    assert qkv.dim() == 3 and qkv.is_contiguous()
+    B, T, three_d = qkv.shape
+    hd = three_d // (3 * num_heads)
+    assert three_d == 3 * num_heads * hd
+    return B, T, hd
+
+
+def attention_fwd_lse(qkv, num_heads, scale, out=None, lse=None):
+    """qkv half [B,T,3*H*64], the RAW output of the qkv Linear (q not pre-scaled) ->
+    (out half [B,T,H*64] = softmax(scale q k^T) v, lse fp32 [B,H,Tp]): the log-sum-exp of
+    the scaled scores in log2 units, rows padded to ``attention_stats_len(T)``; columns
+    T.. of lse are not written."""
+    dev = _dev(qkv)
+    B, T, hd = _qkv_dims(qkv, num_heads)
+    if out is None:
+        out = torch.empty((B, T, num_heads * hd), dtype=_half.dtype(), device=dev)
+    if lse is None:
+        lse = torch.empty((B, num_heads, attention_stats_len(T)), dtype=torch.float32,
+                          device=dev)
+    assert lse.is_contiguous() and lse.dtype == torch.float32
+    _lib.launch('veon_vit_attention_fwd_lse', dev, qkv, out, lse, B, T, num_heads, hd,
+                float(scale))
+    return out, lse
+
+
+def attention_bwd(qkv, out, dout, lse, num_heads, scale, dqkv=None, workspace=None):
+    """Backward of ``attention_fwd_lse``: dout half [B,T,H*64] and the saved qkv, out, lse
+    -> dqkv half [B,T,3*H*64], every element written.  ``workspace``: fp32 [B,H,Tp] for
+    delta = rowsum(dout * out) (allocated when None).  No atomics: deterministic.  In the
+    fp16 flavour the gradients are fp16 as they are: loss scaling is the caller's."""
+    dev = _dev(qkv, out, dout, lse)
+    B, T, hd = _qkv_dims(qkv, num_heads)
+    _lib.require_half(out, dout)
+    assert out.is_contiguous() and dout.is_contiguous() and out.shape == dout.shape
+    assert out.shape == (B, T, num_heads * hd)
+    Tp = attention_stats_len(T)
+    assert lse.is_contiguous() and lse.dtype == torch.float32
+    assert lse.shape == (B, num_heads, Tp)
+    nbytes = int(_lib.lib().veon_vit_attention_bwd_workspace_bytes(B, T, num_heads))
+    if nbytes < 0:
+        raise _lib.VeonHipError('attention_bwd: unsupported shape')
+    if workspace is None:
+        workspace = torch.empty((B, num_heads, Tp), dtype=torch.float32, device=dev)
+    assert workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= nbytes
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    assert dqkv.is_contiguous() and dqkv.shape == qkv.shape and dqkv.dtype == qkv.dtype
+    _lib.launch('veon_vit_attention_bwd', dev, qkv, out, dout, lse, dqkv, workspace,
+                workspace.numel() * workspace.element_size(), B, T, num_heads, hd,
+                float(scale))
+    return dqkv
+
+
+def attention_ref(qkv, num_heads, scale):
+    """softmax(scale q k^T) v in torch, in the operand's own dtype: qkv [B,T,3*H*hd] ->
+    [B,T,H*hd] (the arithmetic of the DINOv2 ``Attention`` module)."""
+    B, T, three_d = qkv.shape
+    q, k, v = qkv.reshape(B, T, 3, num_heads, -1).permute(2, 0, 3, 1, 4)
+    attn = ((q * scale) @ k.transpose(-2, -1)).softmax(dim=-1)
+    return (attn @ v).transpose(1, 2).reshape(B, T, three_d // 3)
+
+
+def attention_bwd_ref(qkv, dout, num_heads, scale):
+    """``attention_bwd`` in torch, in the operands' own dtype (pass fp64 for a reference):
+    the closed form dV = P^T dO, dS = P o (dP - delta), dQ = scale dS K, dK = scale dS^T Q
+    with the T x T matrices formed explicitly."""
+    B, T, three_d = qkv.shape
+    q, k, v = qkv.reshape(B, T, 3, num_heads, -1).permute(2, 0, 3, 1, 4)
+    do = dout.reshape(B, T, num_heads, -1).permute(0, 2, 1, 3)
+    p = ((q * scale) @ k.transpose(-2, -1)).softmax(dim=-1)
+    o = p @ v
+    dv = p.transpose(-2, -1) @ do
+    dp = do @ v.transpose(-2, -1)
+    ds = p * (dp - (do * o).sum(-1, keepdim=True))
+    dq = (ds @ k) * scale
+    dk = (ds.transpose(-2, -1) @ q) * scale
+    return torch.stack((dq, dk, dv)).permute(1, 3, 0, 2, 4).reshape(B, T, three_d)
+
+
+class _AttentionTrainFn(torch.autograd.Function):
+    """Saves qkv, out and lse (B*H*Tp floats): never a T x T tensor."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads, scale):
+        out, lse = attention_fwd_lse(qkv.contiguous(), num_heads, scale)
+        ctx.num_heads, ctx.scale = num_heads, scale
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        return attention_bwd(qkv.contiguous(), out, dout.contiguous(), lse, ctx.num_heads,
+                             ctx.scale), None, None
+
+
+def attention_train(qkv, num_heads, scale):
+    """``attention_fwd_lse``'s out under autograd, backward on ``attention_bwd``."""
+    return _AttentionTrainFn.apply(qkv, num_heads, scale)
+
+
 class BlockWeights:
     """Device weights of one transformer block packed for ``veon_vit_block``
     (include/veon_hip.h): keeps the tensors alive and the C struct ready."""
