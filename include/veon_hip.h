@@ -1002,6 +1002,45 @@ int veon_vit_attention_bwd(const void *qkv, const void *out, const void *dout,
                            int64_t workspace_bytes, int B, int T, int H, int head_dim,
                            float scale, void *stream);
 
+/* ======== temporal_train.hip ======================================================== */
+
+/*
+ * Backward of veon_deform_attention_bf16, the sampling + attention core of
+ * TemporalDeformable.forward (align_net_occ3d.py:138-196), with the same operands, shape
+ * limits and meaning of `off_padded` (RAW offsets, off_channels >= heads*samples*3, the
+ * surplus ignored).  The forward stores nothing: positions are recomputed bit for bit.
+ * `workspace`: veon_deform_attention_bwd_workspace_bytes(B, Z, Y, X, heads) bytes
+ * (host-only; -1: bad shape), 64 bytes per (voxel, head): the fp32 pairs
+ * (hd^-0.5 dlogit_s, softmax weight_s) of the 8 samples.
+ *
+ * veon_deform_attention_bwd_bf16 (align_net_occ3d.py:138-196): from dout (C channels)
+ * writes dq (C channels) and doff (off_channels channels: the gradient of the RAW offsets,
+ * through tanh; surplus channels zero) with ZERO halos, and the workspace.  ATen's
+ * grid_sample conventions: no offset gradient on an axis whose clamped coordinate lies on
+ * or beyond the border (f <= 0 or f >= n - 1), the right-hand derivative at a node.
+ *
+ * veon_deform_attention_bwd_dkv_bf16 (align_net_occ3d.py:138-196): dkv (2*C channels, every
+ * row written, halo zero) from the workspace the call above filled.  `ranges`: DEVICE ints,
+ * (lo, hi) inclusive pairs (hi < lo: empty), X pairs of source z indices per target x, then
+ * Y pairs of source y per target y, then Z pairs of source x per target z: a superset of
+ * the voxels whose samples can touch that target coordinate (the X position of a sample is
+ * driven by its voxel's z index, the Z position by x).  A gather over that box in a fixed
+ * order: no atomics, repeated calls are bit-identical.  Outputs must not alias inputs.
+ */
+int64_t veon_deform_attention_bwd_workspace_bytes(int B, int Z, int Y, int X, int heads);
+int veon_deform_attention_bwd_bf16(const void *kv_padded, const void *q_padded,
+                                   const void *off_padded, const void *dout_padded,
+                                   void *dq_padded, void *doff_padded, void *workspace,
+                                   int64_t workspace_bytes, int B, int Z, int Y, int X,
+                                   int C, int heads, int samples, int off_channels,
+                                   void *stream);
+int veon_deform_attention_bwd_dkv_bf16(const void *q_padded, const void *off_padded,
+                                       const void *dout_padded, const void *workspace,
+                                       int64_t workspace_bytes, const int *ranges,
+                                       void *dkv_padded, int B, int Z, int Y, int X, int C,
+                                       int heads, int samples, int off_channels,
+                                       void *stream);
+
 /* ======== occ_head.hip ============================================================== */
 
 /* Tail of the occupancy path in one kernel (semantic_net/san_in_veon_temporal.py:

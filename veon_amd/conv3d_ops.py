@@ -69,6 +69,11 @@ class PaddedVolume(_PaddedGrid):
     def __init__(self, B, C, Z, Y, X, device):
         super().__init__((B, C, Z, Y, X), device)
 
+    @staticmethod
+    def rows_of(shape):
+        """M of the padded grid of a (B, C, Z, Y, X) volume (guard rows not counted)."""
+        return int(shape[0]) * math.prod(int(v) + 2 for v in shape[2:])
+
 
 class PaddedImage(_PaddedGrid):
     """(B,C,Y,X) images as a zero-haloed channels-last bf16 grid
@@ -354,6 +359,212 @@ def deform_attention(kv, q, off, heads, samples=8, out=None):
     _lib.launch('veon_deform_attention_bf16', dev, kv.rows, q.rows, off.rows, out.rows,
                 B, Z, Y, X, C, heads, samples, off.shape[1])
     return out
+
+
+# ------------------------------------ training of the deformable attention (temporal)
+DEFORM_SAMPLES = 8
+DEFORM_RANGE_SLOP = 1e-3     # voxels; far above the fp32 error of a position (< 1e-4)
+
+
+def deform_attention_bwd_ref(kv, q, off, dout, heads):
+    """The dense closed form of the backward of ``TemporalDeformable.attend`` in plain
+    torch, on any device and in the dtype of its inputs -- the mathematics
+    ``deform_attention_bwd`` implements (csrc/temporal_train.hip).  ``kv`` (B,2C,Z,Y,X)
+    per head [key | value], ``q`` and ``dout`` (B,C,Z,Y,X), ``off`` (B, >= heads*24,
+    Z,Y,X) RAW offsets -> (dkv, dq, doff) of those shapes; doff is the gradient of the
+    raw offsets (through tanh), zero in the surplus channels.
+
+    Per voxel, head and sample s (K_s, V_s the trilinear samples, scale = hd^-0.5):
+    a = softmax_s(scale q.K_s); da_s = dout.V_s; dl_s = a_s (da_s - sum_t a_t da_t);
+    dq = scale sum_s dl_s K_s; g_s = [scale dl_s q | a_s dout] is scattered to the 8
+    corner rows with their weights; the position gradient along an axis is
+    sum_c (+-1) (product of the other two axes' weights) (row_c . g_s), times
+    0.5 (n_dst - 1) / n_src (1 - tanh^2).  ATen's conventions: the position gradient is
+    zero on an axis where the coordinate f <= 0 or f >= n - 1 (the clamp, the border
+    mode, axes of length one), and at a node ``floor`` gives the right-hand derivative.
+    The axis quirk of the forward is kept: offset component 0 and the z index place the
+    sample along X (divided by Z), component 2 and the x index along Z (divided by X)."""
+    B, C, Z, Y, X = q.shape
+    S, hd, N = DEFORM_SAMPLES, C // heads, Z * Y * X
+    dt, dev = q.dtype, q.device
+    scale = hd ** -0.5
+    o = torch.tanh(off[:, :heads * S * 3].reshape(B, heads, S, 3, Z, Y, X))
+    base = [torch.linspace(-1, 1, n, dtype=dt, device=dev).view(shape)
+            for n, shape in ((Z, (Z, 1, 1)), (Y, (1, Y, 1)), (X, (1, 1, X)))]
+    n_src, n_dst = (Z, Y, X), (X, Y, Z)
+    i0, i1, t, jac = [], [], [], []
+    for a in range(3):
+        g = (base[a] + o[:, :, :, a] / n_src[a]).clamp(-1, 1)
+        n = n_dst[a]
+        f = (g + 1) * 0.5 * (n - 1)
+        lo = f.floor().clamp(max=n - 1)
+        i0.append(lo.long())
+        i1.append((lo.long() + 1).clamp(max=n - 1))
+        t.append(f - lo)
+        inside = ((f > 0) & (f < n - 1)).to(dt)
+        jac.append(inside * (0.5 * (n - 1) / n_src[a]) * (1 - o[:, :, :, a] ** 2))
+    kvh = kv.reshape(B, heads, 2 * hd, N)
+    qh = q.reshape(B, heads, hd, 1, N)
+    do = dout.reshape(B, heads, hd, 1, N)
+
+    def flat(v):                         # (B,heads,S,Z,Y,X) -> (B,heads,1,S,N)
+        return v.reshape(B, heads, 1, S, N)
+    corners = []
+    samp = 0
+    for c in range(8):
+        xs, wx = (i1[0], t[0]) if c & 1 else (i0[0], 1 - t[0])
+        ys, wy = (i1[1], t[1]) if c & 2 else (i0[1], 1 - t[1])
+        zs, wz = (i1[2], t[2]) if c & 4 else (i0[2], 1 - t[2])
+        idx = ((zs * Y + ys) * X + xs).reshape(B, heads, 1, S * N).expand(-1, -1, 2 * hd, -1)
+        rows = kvh.gather(3, idx).reshape(B, heads, 2 * hd, S, N)
+        corners.append((idx, rows, flat(wx), flat(wy), flat(wz)))
+        samp = samp + flat(wz * wy * wx) * rows
+    K, V = samp[:, :, :hd], samp[:, :, hd:]
+    a_ = (scale * (qh * K).sum(2)).softmax(dim=2)                  # (B,heads,S,N)
+    da = (do * V).sum(2)
+    dl = a_ * (da - (a_ * da).sum(2, keepdim=True))
+    dq = scale * (dl.unsqueeze(2) * K).sum(3)
+    g = torch.cat([scale * dl.unsqueeze(2) * qh, a_.unsqueeze(2) * do], dim=2)
+    dkv = torch.zeros_like(kvh)
+    dpos = [0, 0, 0]
+    for c, (idx, rows, wx, wy, wz) in enumerate(corners):
+        dkv.scatter_add_(3, idx, ((wz * wy * wx) * g).reshape(B, heads, 2 * hd, S * N))
+        d = (rows * g).sum(2, keepdim=True)
+        dpos[0] = dpos[0] + (1 if c & 1 else -1) * wz * wy * d
+        dpos[1] = dpos[1] + (1 if c & 2 else -1) * wz * wx * d
+        dpos[2] = dpos[2] + (1 if c & 4 else -1) * wy * wx * d
+    doff = torch.zeros_like(off)
+    doff[:, :heads * S * 3] = torch.stack(
+        [dpos[a].reshape(B, heads, S, Z, Y, X) * jac[a] for a in range(3)],
+        dim=3).reshape(B, heads * S * 3, Z, Y, X)
+    return dkv.reshape(kv.shape), dq.reshape(q.shape), doff
+
+
+def deform_range_bound(n_src, n_dst):
+    """Largest number of source indices ``deform_candidate_ranges`` can list for one
+    target index: centres (n_dst-1)/(n_src-1) voxels apart, each reaching
+    (n_dst-1)/(2 n_src) to either side, against a window of 1 + slop to either side."""
+    if n_src == 1 or n_dst == 1:
+        return n_src
+    step = (n_dst - 1) / (n_src - 1)
+    reach = 1 + DEFORM_RANGE_SLOP + (n_dst - 1) / (2 * n_src)
+    return min(n_src, int(math.floor(2 * reach / step)) + 1)
+
+
+def _deform_axis_ranges(n_src, n_dst):
+    i = torch.arange(n_src, dtype=torch.float64)
+    c = -1 + 2 * i / (n_src - 1) if n_src > 1 else torch.full((1,), -1.0, dtype=torch.float64)
+    flo = ((c - 1.0 / n_src).clamp(-1, 1) + 1) * 0.5 * (n_dst - 1)
+    fhi = ((c + 1.0 / n_src).clamp(-1, 1) + 1) * 0.5 * (n_dst - 1)
+    tgt = torch.arange(n_dst, dtype=torch.float64).view(-1, 1)
+    # a sample at f gives weight to node t iff t - 1 < f < t + 1
+    hit = (fhi.view(1, -1) >= tgt - 1 - DEFORM_RANGE_SLOP) & \
+        (flo.view(1, -1) <= tgt + 1 + DEFORM_RANGE_SLOP)
+    lo = hit.int().argmax(1)
+    hi = n_src - 1 - hit.flip(1).int().argmax(1)
+    none = ~hit.any(1)
+    lo[none], hi[none] = 0, -1
+    return torch.stack([lo, hi], dim=1).to(torch.int32)
+
+
+def deform_candidate_ranges(Z, Y, X):
+    """The three (n, 2) int32 tables of inclusive (lo, hi) source indices whose samples
+    can touch a target coordinate of the deformable attention (hi < lo: none):
+    [0] per target x the source z (the X position is driven by the z index), [1] per
+    target y the source y, [2] per target z the source x.  Along an axis source index i
+    has centre c_i = -1 + 2i/(n_src-1) and reaches +-1/n_src (|tanh| <= 1), clamped to
+    [-1, 1]; its coordinate range [flo_i, fhi_i] is monotone in i, so the indices that
+    reach (t-1, t+1) are one contiguous run.  fp64 on the host, widened by
+    ``DEFORM_RANGE_SLOP`` voxels; over-inclusion is harmless (the weight comes out 0)."""
+    return (_deform_axis_ranges(Z, X), _deform_axis_ranges(Y, Y), _deform_axis_ranges(X, Z))
+
+
+_DEFORM_TABLES = {}
+
+
+def _deform_tables(Z, Y, X, dev):
+    key = (Z, Y, X, str(dev))
+    t = _DEFORM_TABLES.get(key)
+    if t is None:
+        t = torch.cat([r.reshape(-1) for r in deform_candidate_ranges(Z, Y, X)]).to(dev)
+        _DEFORM_TABLES[key] = t
+    return t
+
+
+def deform_attention_bwd(kv, q, off, dout, heads, need_dkv=True, out=None):
+    """Backward of ``deform_attention`` on PaddedVolumes -> (dkv, dq, doff), half volumes
+    with zero halos; ``doff`` has the channels of ``off`` (gradient of the RAW offsets,
+    surplus channels zero).  ``need_dkv`` False: the dKV kernel is not launched and dkv
+    is None.  ``out``: (dkv, dq, doff) volumes to write into.  Nothing is accumulated
+    with atomics: repeated calls give the same bits."""
+    dev = _lib.require_device(kv.storage, q.storage, off.storage, dout.storage)
+    B, C, Z, Y, X = q.shape
+    assert kv.shape == (B, 2 * C, Z, Y, X) and dout.shape == q.shape
+    assert off.shape[0] == B and tuple(off.shape[2:]) == (Z, Y, X)
+    _lib.require_half(kv.rows, q.rows, off.rows, dout.rows)
+    dkv, dq, doff = out if out is not None else (None, None, None)
+    if dq is None:
+        dq = q.like()
+    if doff is None:
+        doff = off.like()
+    assert dq.shape == q.shape and doff.shape == off.shape
+    assert dq is not q and dq is not dout and doff is not off
+    nbytes = int(_lib.lib().veon_deform_attention_bwd_workspace_bytes(B, Z, Y, X, heads))
+    if nbytes < 0:
+        raise _lib.VeonHipError('deform_attention_bwd: unsupported shape %s' % (q.shape,))
+    ws = _workspace('deform', nbytes, dev, B, Z, Y, X, heads)
+    _lib.launch('veon_deform_attention_bwd_bf16', dev, kv.rows, q.rows, off.rows, dout.rows,
+                dq.rows, doff.rows, ws, nbytes, B, Z, Y, X, C, heads, DEFORM_SAMPLES,
+                off.shape[1])
+    if not need_dkv:
+        return None, dq, doff
+    if dkv is None:
+        dkv = kv.like()
+    assert dkv.shape == kv.shape and dkv is not kv
+    _lib.launch('veon_deform_attention_bwd_dkv_bf16', dev, q.rows, off.rows, dout.rows, ws,
+                nbytes, _deform_tables(Z, Y, X, dev), dkv.rows, B, Z, Y, X, C, heads,
+                DEFORM_SAMPLES, off.shape[1])
+    return dkv, dq, doff
+
+
+class _DeformAttentionFn(torch.autograd.Function):
+    """``deform_attention`` under autograd on the STORAGE tensors of PaddedVolumes (as
+    ``_ResBlockTrainFn``): saves its three inputs and nothing else."""
+
+    @staticmethod
+    def forward(ctx, kvs, qs, offs, heads, shape):
+        B, C, Z, Y, X = shape
+        vol = PaddedVolume.from_storage
+        kv = vol(kvs, (B, 2 * C, Z, Y, X))
+        q = vol(qs, shape)
+        off = vol(offs, (B, offs.shape[1], Z, Y, X))
+        ctx.heads, ctx.shape = heads, tuple(shape)
+        ctx.save_for_backward(kvs, qs, offs)
+        return deform_attention(kv, q, off, heads).storage
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, douts):
+        kvs, qs, offs = ctx.saved_tensors
+        B, C, Z, Y, X = ctx.shape
+        vol = PaddedVolume.from_storage
+        need_kv, need_q, need_off = ctx.needs_input_grad[:3]
+        dkv, dq, doff = deform_attention_bwd(
+            vol(kvs, (B, 2 * C, Z, Y, X)), vol(qs, ctx.shape),
+            vol(offs, (B, offs.shape[1], Z, Y, X)), vol(douts.contiguous(), ctx.shape),
+            ctx.heads, need_dkv=need_kv)
+        return (dkv.storage if need_kv else None, dq.storage if need_q else None,
+                doff.storage if need_off else None, None, None)
+
+
+def deform_attention_train(kv, q, off, heads, shape):
+    """``deform_attention`` under autograd.  ``kv``, ``q``, ``off``: the storage tensors
+    of PaddedVolumes (guard rows included) of 2C, C and >= heads*24 channels on the grid
+    ``shape`` = (B, C, Z, Y, X) of ``q``; ``off`` holds the RAW offsets.  -> the storage of
+    the fused volume (C channels).  The forward is the inference kernel and saves only
+    its inputs; the backward (csrc/temporal_train.hip) recomputes the sample positions
+    and launches no dKV kernel when ``kv`` needs no gradient."""
+    return _DeformAttentionFn.apply(kv, q, off, heads, tuple(int(v) for v in shape))
 
 
 def warp_volume(vol, affine, out=None):

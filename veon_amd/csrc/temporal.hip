@@ -17,12 +17,13 @@
 // per corner, fp32 accumulation.
 #include <hip/hip_runtime.h>
 
+#include "deform_pos.h"
 #include "mfma_common.h"
 #include "veon_hip.h"
 
 namespace {
 
-constexpr int kSamples = 8;
+constexpr int kSamples = kDeformSamples;
 
 __device__ __forceinline__ void fma8(float (&acc)[8], float w, const bf16x8 v) {
 #pragma unroll
@@ -66,10 +67,7 @@ __global__ __launch_bounds__(256) void k_deform_attn(
 #pragma unroll
     for (int k = 0; k < 8; ++k) qv[k] = is_val ? 0.f : bf2f((bf16_t)t[k]) * qscale;
   }
-  // torch.linspace(-1, 1, n)[i]
-  const float zn = Z > 1 ? -1.f + 2.f * z / (Z - 1) : -1.f;
-  const float yn = Y > 1 ? -1.f + 2.f * y / (Y - 1) : -1.f;
-  const float xn = X > 1 ? -1.f + 2.f * x / (X - 1) : -1.f;
+  const float zn = deform_base(z, Z), yn = deform_base(y, Y), xn = deform_base(x, X);
   const bf16_t* orow = off + row * off_stride + h * kSamples * 3;
   const bf16_t* kvh = kv + h * 2 * HD + j * 8;
   const int64_t kvc = 2 * C;
@@ -78,22 +76,10 @@ __global__ __launch_bounds__(256) void k_deform_attn(
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll 2
   for (int s = 0; s < kSamples; ++s) {
-    // The reference stacks its base grid (z, y, x) and divides by (D, H, W), and
-    // grid_sample reads that last axis as (x, y, z): component 0 -- built from
-    // the z index -- is the position along X, component 2 the one along Z.
-    const float o0 = tanhf(bf2f(orow[s * 3 + 0]));
-    const float o1 = tanhf(bf2f(orow[s * 3 + 1]));
-    const float o2 = tanhf(bf2f(orow[s * 3 + 2]));
-    const float gx = fminf(fmaxf(zn + o0 / Z, -1.f), 1.f);
-    const float gy = fminf(fmaxf(yn + o1 / Y, -1.f), 1.f);
-    const float gz = fminf(fmaxf(xn + o2 / X, -1.f), 1.f);
-    const float fx = (gx + 1.f) * 0.5f * (X - 1);
-    const float fy = (gy + 1.f) * 0.5f * (Y - 1);
-    const float fz = (gz + 1.f) * 0.5f * (Z - 1);
-    const int x0 = min((int)floorf(fx), X - 1), y0 = min((int)floorf(fy), Y - 1),
-              z0 = min((int)floorf(fz), Z - 1);
-    const float tx = fx - x0, ty = fy - y0, tz = fz - z0;
-    const int x1 = min(x0 + 1, X - 1), y1 = min(y0 + 1, Y - 1), z1 = min(z0 + 1, Z - 1);
+    // positions: deform_pos.h (shared with the backward)
+    const DeformPos sp = deform_pos(orow + s * 3, zn, yn, xn, Z, Y, X);
+    const int x0 = sp.x0, y0 = sp.y0, z0 = sp.z0, x1 = sp.x1, y1 = sp.y1, z1 = sp.z1;
+    const float tx = sp.tx, ty = sp.ty, tz = sp.tz;
     float samp[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < 8; ++c) {

@@ -296,6 +296,62 @@ class _ResBlockTrainFn(torch.autograd.Function):
                 wgrad(dw2, w2), s2[1].to(g2.dtype), s2[0].to(g2.dtype), None, None)
 
 
+class _ConvModuleTrainFn(torch.autograd.Function):
+    """One training step of a ``ConvModule3d`` (3x3x3 conv -> train-mode BN -> ReLU) on
+    padded rows: the single-conv sibling of ``_ResBlockTrainFn`` (no identity), built from
+    the same ``conv3d_ops`` calls, storage tensors in and out.  Cin and Cout may differ.
+    Saved: the input, the stored conv output y, the activation, mean and rstd.  No data
+    gradient is computed for an input that needs none (a past frame)."""
+
+    @staticmethod
+    def forward(ctx, xs, w, g, b, shape, cm):
+        x = conv3d_ops.PaddedVolume.from_storage(xs, shape)
+        y = conv3d_ops.conv3d_k3(x, conv3d_ops.pack_weight(w))
+        mu, r, sc, sh = _bn_train_native(y, cm.bn)
+        a = conv3d_ops.bn_apply(y, sc, sh, relu=True)
+        ctx.shape, ctx.half = tuple(shape), _half.dtype()
+        ctx.save_for_backward(xs, y.storage, a.storage, mu, r, w, g)
+        return a.storage
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        xs, ys, as_, mu, r, w, g = ctx.saved_tensors
+        B, _, Z, Y, X = ctx.shape
+        oshape = (B, w.shape[0], Z, Y, X)
+        vol = conv3d_ops.PaddedVolume.from_storage
+        x, y, a = vol(xs, ctx.shape), vol(ys, oshape), vol(as_, oshape)
+        da = vol(dout.contiguous(), oshape)
+        n = B * Z * Y * X
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        s = conv3d_ops.bn_bwd_sums(da, a, y, mu, r)
+        dy = conv3d_ops.bn_bwd_apply(da, a, y, *conv3d_ops.bn_bwd_coefficients(s, n, g, mu, r))
+        dw = conv3d_ops.conv3d_k3_wgrad(dy, x) if need_w else None
+        dxs = None
+        if need_x:
+            dxs = conv3d_ops.conv3d_k3(dy, conv3d_ops.pack_weight_dgrad(w).to(ctx.half)).storage
+        return (dxs, conv3d_ops.wgrad_to_param(dw, w), s[1].to(g.dtype), s[0].to(g.dtype),
+                None, None)
+
+
+def conv_module_train_ok(cm):
+    """Whether ``_ConvModuleTrainFn`` can run the ConvModule3d ``cm`` (3x3x3, stride 1, no
+    conv bias, train-mode BN with buffers, ReLU, widths the weight gradient supports)."""
+    c = cm.conv
+    return (c.kernel_size == (3, 3, 3) and c.stride == (1, 1, 1) and c.padding == (1, 1, 1)
+            and c.bias is None and c.weight.dtype == torch.float32
+            and conv3d_ops.wgrad_supported(c.in_channels, c.out_channels)
+            and cm.bn is not None and cm.bn.training and cm.bn.affine
+            and cm.bn.track_running_stats and cm.activate is not None)
+
+
+def conv_module_train(cm, xs, shape):
+    """``cm`` on the storage ``xs`` of a PaddedVolume of ``shape`` -> (storage, shape)."""
+    out = _ConvModuleTrainFn.apply(xs, cm.conv.weight, cm.bn.weight, cm.bn.bias,
+                                   tuple(shape), cm)
+    return out, (shape[0], cm.conv.out_channels) + tuple(shape[2:])
+
+
 class _PackFn(torch.autograd.Function):
     """(B,C,Z,Y,X) fp32 -> storage of its PaddedVolume; backwards the unpack."""
 

@@ -30,7 +30,9 @@ import torch.nn.functional as F
 
 from ... import conv3d_ops, vit_ops
 from .._native_cache import NativeCacheMixin
-from .align_net_body import ConvModule3d
+from .._train_fns import _LinearTrainFn
+from .align_net_body import (ConvModule3d, _PackFn, _UnpackFn, conv_module_train,
+                             conv_module_train_ok)
 from ... import half as _half
 
 
@@ -60,6 +62,97 @@ def _cat(vols):
     out.storage = torch.cat([v.storage for v in vols], dim=1)
     out.rows = out.storage[out.guard:out.guard + out.M]
     return out
+
+
+# ------------------------------------------------- native training (storage tensors)
+# The differentiable values of the native training path are the STORAGE tensors of
+# PaddedVolumes (half, guard rows included), as in ``_ResBlockTrainFn``; ``shape`` is the
+# (B, C, Z, Y, X) of the volume a storage tensor holds.
+def _rows_linear(xs, shape, w, b):
+    """1x1x1 conv as ``_LinearTrainFn`` on the rows of the padded grid -> storage.  The
+    halo rows of the result hold the bias (zeros without one); the guard rows are zero."""
+    guard = (xs.shape[0] - conv3d_ops.PaddedVolume.rows_of(shape)) // 2
+    y = _LinearTrainFn.apply(xs[guard:xs.shape[0] - guard], w.view(w.shape[0], -1), b)
+    return F.pad(y, (0, 0, guard, guard))
+
+
+class _ConvBiasTrainFn(torch.autograd.Function):
+    """3x3x3 conv (+ bias) on padded rows, no norm, no activation: the stored output is
+    the pre-activation.  Backward: bias gradient (``colsum``), MFMA weight gradient, data
+    gradient through the forward kernel.  The incoming gradient has a zero halo."""
+
+    @staticmethod
+    def forward(ctx, xs, w, b, shape):
+        x = conv3d_ops.PaddedVolume.from_storage(xs, shape)
+        shift = None if b is None else b.detach().float().contiguous()
+        ctx.shape, ctx.half = tuple(shape), _half.dtype()
+        ctx.save_for_backward(xs, w)
+        return conv3d_ops.conv3d_k3(x, conv3d_ops.pack_weight(w), None, shift).storage
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dys):
+        xs, w = ctx.saved_tensors
+        B, _, Z, Y, X = ctx.shape
+        vol = conv3d_ops.PaddedVolume.from_storage
+        x, dy = vol(xs, ctx.shape), vol(dys.contiguous(), (B, w.shape[0], Z, Y, X))
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        db = vit_ops.colsum(dy.rows).to(w.dtype) if need_b else None
+        dw = conv3d_ops.wgrad_to_param(conv3d_ops.conv3d_k3_wgrad(dy, x), w) if need_w else None
+        dxs = None
+        if need_x:
+            dxs = conv3d_ops.conv3d_k3(dy, conv3d_ops.pack_weight_dgrad(w).to(ctx.half)).storage
+        return dxs, dw, db, None
+
+
+class _GeluVolFn(torch.autograd.Function):
+    """Exact GELU on a storage tensor from the saved pre-activation (zero stays zero: the
+    halo survives in both directions)."""
+
+    @staticmethod
+    def forward(ctx, ys):
+        ctx.save_for_backward(ys)
+        return vit_ops.gelu(ys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh):
+        ys, = ctx.saved_tensors
+        return vit_ops.gelu_bwd(dh.contiguous(), ys)
+
+
+class _BNReLUTrainFn(torch.autograd.Function):
+    """Train-mode BatchNorm3d + ReLU of a stored volume ``ys`` with a ZERO halo.  ``bias``
+    is the bias of the 1x1x1 conv that produced ``ys`` WITHOUT adding it (so the halo
+    stayed zero): a per-channel constant ahead of train-mode BN cancels in the output and
+    has zero gradient, so it only enters the running mean."""
+
+    @staticmethod
+    def forward(ctx, ys, g, b, bias, shape, bn):
+        y = conv3d_ops.PaddedVolume.from_storage(ys, shape)
+        B, C, Z, Y, X = shape
+        n = B * Z * Y * X
+        mean, var, rstd = conv3d_ops.bn_batch_stats(conv3d_ops.bn_sums(y), n, bn.eps)
+        conv3d_ops.bn_update_running(bn, mean + bias.detach().double(), var, n)
+        scale = g.detach().double() * rstd
+        shift = b.detach().double() - mean * scale
+        a = conv3d_ops.bn_apply(y, scale.float(), shift.float(), relu=True)
+        ctx.shape = tuple(shape)
+        ctx.save_for_backward(ys, a.storage, mean.float(), rstd.float(), g, bias)
+        return a.storage
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        ys, as_, mu, r, g, bias = ctx.saved_tensors
+        B, C, Z, Y, X = ctx.shape
+        vol = conv3d_ops.PaddedVolume.from_storage
+        y, a, da = vol(ys, ctx.shape), vol(as_, ctx.shape), vol(dout.contiguous(), ctx.shape)
+        n = B * Z * Y * X
+        s = conv3d_ops.bn_bwd_sums(da, a, y, mu, r)
+        dy = conv3d_ops.bn_bwd_apply(da, a, y, *conv3d_ops.bn_bwd_coefficients(s, n, g, mu, r))
+        return (dy.storage, s[1].to(g.dtype), s[0].to(g.dtype),
+                torch.zeros_like(bias) if ctx.needs_input_grad[3] else None, None, None)
 
 
 class BeforeFusionLayer(nn.Module):
@@ -100,7 +193,19 @@ class TemporalFusionMultiFrameMiddle3x3Seq(nn.Module):
 class TemporalDeformable(NativeCacheMixin, nn.Module):
     """Deformable cross-frame attention (align_net_occ3d.py:89-204): queries and
     sampling offsets from one volume, keys/values sampled trilinearly from the
-    other at ``num_samples`` points per head, softmax over the samples."""
+    other at ``num_samples`` points per head, softmax over the samples.
+
+    ``hip_train`` (class attribute, default False): opt-in native TRAINING path.  When
+    set, a training-mode module on ROCm fp32 tensors (or, inside
+    ``TemporalFusionMultiFrame``, on the storage tensors of PaddedVolumes) whose widths
+    the kernels support trains on padded half rows: projections as GEMMs with MFMA weight
+    gradients, the offset convs on the implicit-GEMM kernel, the deformable attention and
+    its backward in csrc/temporal.hip / temporal_train.hip, train-mode BatchNorm passes.
+    ``out_proj`` runs without its bias there (it cancels in train-mode BN; it enters the
+    running mean, and its gradient is exactly zero).  As on the other native training
+    paths, the inner modules are not called: hooks registered on them do not fire."""
+
+    hip_train = False
 
     def __init__(self, channels, num_heads=4, num_samples=8):
         super().__init__()
@@ -149,9 +254,53 @@ class TemporalDeformable(NativeCacheMixin, nn.Module):
     def forward(self, feat_prev, feat_curr):
         if _fast(feat_curr):
             return self.hip_forward(feat_prev, feat_curr)
+        if self.hip_train_ok(feat_prev, feat_curr):
+            shape = tuple(feat_curr.shape)
+            out = self.train_native(_PackFn.apply(feat_prev), _PackFn.apply(feat_curr), shape)
+            return _UnpackFn.apply(out, shape)
         fused = self.attend(self.key_value_proj(feat_prev), self.query_proj(feat_curr),
                             self.offset_conv(feat_curr))
         return self.out_activate(self.final_norm(self.out_proj(fused)))
+
+    # ------------------------------------------------------- native training
+    def train_supported(self):
+        """Widths and parameters the native training chain takes: C % 64 == 0, head dim
+        32 or 64, 8 samples, fp32 parameters, train-mode BN with buffers."""
+        bn = self.final_norm
+        return (self.channels % 64 == 0 and self.head_dim in (32, 64)
+                and self.num_samples == conv3d_ops.DEFORM_SAMPLES
+                and self.num_heads * 2 * (self.head_dim // 8) <= 64
+                and 64 % (self.num_heads * 2 * (self.head_dim // 8)) == 0
+                and all(p.dtype == torch.float32 for p in self.parameters())
+                and bn.training and bn.affine and bn.track_running_stats)
+
+    def hip_train_ok(self, *xs):
+        return (self.hip_train and self.training and self.train_supported()
+                and all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+                        and x.dim() == 5 for x in xs))
+
+    def project_kv_train(self, prev_s, shape):
+        """key/value projection of the sampled volume (storage in, storage out); both
+        calls of ``TemporalFusionDeformMiddle`` share it and autograd adds their dKV."""
+        return _rows_linear(prev_s, shape, self.key_value_proj.weight, self.key_value_proj.bias)
+
+    def train_native(self, prev_s, curr_s, shape, kv_s=None):
+        """The training chain on storage tensors of PaddedVolumes of ``shape``."""
+        B, C, Z, Y, X = shape
+        if kv_s is None:
+            kv_s = self.project_kv_train(prev_s, shape)
+        q_s = _rows_linear(curr_s, shape, self.query_proj.weight, self.query_proj.bias)
+        c1, c2 = self.offset_conv[0], self.offset_conv[2]
+        hid = _GeluVolFn.apply(_ConvBiasTrainFn.apply(curr_s, c1.weight, c1.bias, shape))
+        # output channels zero-padded to the weight gradient's tile (96 -> 128 for four
+        # heads): the op ignores the surplus, F.pad's backward drops the padded rows of dW
+        noff = c2.out_channels
+        w2 = F.pad(c2.weight, (0,) * 8 + (0, -noff % 64))
+        off_s = _ConvBiasTrainFn.apply(hid, w2, None, shape)     # tanh is taken in the op
+        fused = conv3d_ops.deform_attention_train(kv_s, q_s, off_s, self.num_heads, shape)
+        bn = self.final_norm
+        y_s = _rows_linear(fused, shape, self.out_proj.weight, None)
+        return _BNReLUTrainFn.apply(y_s, bn.weight, bn.bias, self.out_proj.bias, shape, bn)
 
     # ------------------------------------------------------------- MFMA path
     _native_cache = ('_hip',)
@@ -223,7 +372,20 @@ class TemporalFusionDeformMiddle(nn.Module):
 class TemporalFusionMultiFrame(nn.Module):
     """(align_net_occ3d.py:49-74) current volume + aligned past volumes -> one
     volume of the same shape.  Accepts (B,C,Z,Y,X) tensors, or PaddedVolumes on
-    the MFMA path (``hip_ok``)."""
+    the MFMA path (``hip_ok``).
+
+    ``hip_train`` (class attribute, default False): opt-in native TRAINING path.  When
+    set, a training-mode call on ROCm fp32 tensors whose widths the kernels support packs
+    once, runs every ``ConvModule3d`` as conv -> train-mode BN -> ReLU on padded half rows
+    (``before_fusion_layer`` frame by frame in the definition's order, each call with its
+    own batch statistics and buffer update), the deformable middle as
+    ``TemporalDeformable.train_native`` with one shared key/value projection, and unpacks
+    once.  Past frames that need no gradient get no data gradient.  Anything else (other
+    widths, CPU tensors, eval mode, the switch off) takes the paths above unchanged.  As
+    on the other native training paths, the inner modules are not called: hooks
+    registered on them do not fire."""
+
+    hip_train = False
 
     def __init__(self, channels, seqs=2):
         super().__init__()
@@ -239,7 +401,39 @@ class TemporalFusionMultiFrame(nn.Module):
                 and self.deform_fusion_layer.t_deform.num_samples == 8
                 and (_fast(x) or x.is_cuda))
 
+    def hip_train_ok(self, cur, prevs):
+        convs = [self.t_final, self.before_fusion_layer.offset_conv] + list(self.t_fuse_mid.t_fuse)
+        return (self.hip_train and self.training and len(prevs) == len(self.t_fuse_mid.t_fuse)
+                and all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+                        and x.dim() == 5 and x.shape == cur.shape for x in [cur] + list(prevs))
+                and self.deform_fusion_layer.t_deform.training
+                and self.deform_fusion_layer.t_deform.train_supported()
+                and all(conv_module_train_ok(cm) for cm in convs))
+
+    def train_native(self, cur_occ_feat, prev_occ_feats):
+        shape = tuple(cur_occ_feat.shape)
+        wide = lambda k: (shape[0], k * shape[1]) + shape[2:]      # noqa: E731
+        before = self.before_fusion_layer.offset_conv
+        feats = [conv_module_train(before, _PackFn.apply(t), shape)[0]
+                 for t in [cur_occ_feat] + list(prev_occ_feats)]
+        cur, prevs = feats[0], feats[1:]
+        past, idx = prevs[-1], 0
+        for frame in prevs[-2::-1]:
+            past = conv_module_train(self.t_fuse_mid.t_fuse[idx],
+                                     torch.cat([frame, past], dim=1), wide(2))[0]
+            idx += 1
+        ref = conv_module_train(self.t_fuse_mid.t_fuse[idx],
+                                torch.cat([cur, past], dim=1), wide(2))[0]
+        td = self.deform_fusion_layer.t_deform
+        kv = td.project_kv_train(ref, shape)
+        a = td.train_native(ref, cur, shape, kv)
+        b = td.train_native(ref, past, shape, kv)
+        out = conv_module_train(self.t_final, torch.cat([ref, a, b], dim=1), wide(3))[0]
+        return _UnpackFn.apply(out, shape)
+
     def forward(self, cur_occ_feat, prev_occ_feats):
+        if not _fast(cur_occ_feat) and self.hip_train_ok(cur_occ_feat, prev_occ_feats):
+            return self.train_native(cur_occ_feat, prev_occ_feats)
         feats = self.before_fusion_layer([cur_occ_feat] + list(prev_occ_feats))
         cur, prevs = feats[0], feats[1:]
         ref, past = self.t_fuse_mid(cur, prevs)
