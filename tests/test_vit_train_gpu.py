@@ -18,6 +18,9 @@ import copy
 import pytest
 import torch
 
+# LSE_BOUND, |lse - fp64| in log2 units, 2^-8 (bf16) / 2^-11 (fp16): stated once, next to the
+# hostile cases that are held to it as well (tests/test_vit_train_hostile_gpu.py)
+from tests.attention_train_refs import LSE_BOUND
 from tests.helpers import flavour, fp16_twin, half_tol  # noqa: F401
 from veon_amd import _lib, half, vit_ops
 from veon_amd.models.depth_anything import dinov2
@@ -37,9 +40,6 @@ SHAPES = [(1, 1, 1),      # single token
           (1, 129, 1),    # one past a 128-row workgroup
           (1, 200, 2),    # several tiles
           WORKLOAD]       # the workload's, computed once per flavour (_case)
-# |lse - fp64| in log2 units: every term of the row sum is a half-rounded P (relative error
-# <= 2^-9 / 2^-12), log2(1 + e) <= 1.45 e, plus fp32 slack
-LSE_BOUND = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
 
 
 @pytest.fixture(autouse=True)

@@ -57,7 +57,9 @@ __device__ __forceinline__ float max_over_rows(float x) {
 // STATS (the training forward, attention_train.hip): q is NOT pre-scaled; the scores are
 // multiplied by ``c_scale`` = scale * log2(e) in the fma the natural-log form spends on
 // log2(e) anyway, and the kernel also writes lse[b][h][q] = log2(l_q) - negm_q, the
-// log-sum-exp of the scaled scores in log2 units (fp32, rows of ``Tp`` floats).  The
+// log-sum-exp of the scaled scores in log2 units (fp32, rows of ``Tp`` floats), l_q summed
+// in fp32 from the weights before their half rounding (out keeps the matrix core's sum
+// of the rounded ones: it is the inference kernel's to the bit).  The
 // other instantiations ignore the three trailing arguments.
 template <bool HAS_BIAS, bool LOG2Q, bool STATS = false>
 __global__ __launch_bounds__(256, 3) void k_attention(
@@ -121,10 +123,17 @@ __global__ __launch_bounds__(256, 3) void k_attention(
   // already shifted.
   f32x4 ol[QT];
   float negm[QT];
+  // STATS: the lane's share of the row sum of the weights BEFORE their half rounding (its
+  // 16 keys of every tile, as a register pair).  lse is taken from it: the backward
+  // rebuilds p = exp2(s c - lse) unrounded, and the largest weight of a row is not 1 here
+  // (the reference stands up to kAttRise below the maximum), so the sum of the rounded
+  // weights of a saturated row carries the full half rounding of that one weight.
+  f32x2 lsum[QT];
 #pragma unroll
   for (int i = 0; i < QT; ++i) {
     ol[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     negm[i] = 0.f;
+    lsum[i] = f32x2{0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
@@ -263,6 +272,7 @@ __global__ __launch_bounds__(256, 3) void k_attention(
 #pragma unroll
         for (int j = 0; j < 4; ++j) on_pairs(o[i][j], cc, true);
         on_pairs(ol[i], cc, true);
+        if (STATS) lsum[i] *= cc;
         negm[i] -= d[i];
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) on_pairs(s[i][kt], dd, false);
@@ -281,6 +291,13 @@ __global__ __launch_bounds__(256, 3) void k_attention(
         for (int kt = 2 * kk; kt < 2 * kk + 2; ++kt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) s[i][kt][r] = __builtin_amdgcn_exp2f(s[i][kt][r]);
+        if (STATS) {
+#pragma unroll
+          for (int kt = 2 * kk; kt < 2 * kk + 2; ++kt) {
+            lsum[i] += f32x2{s[i][kt][0], s[i][kt][1]};
+            lsum[i] += f32x2{s[i][kt][2], s[i][kt][3]};
+          }
+        }
         const u32x4 pk = {pack_bf16(s[i][2 * kk][0], s[i][2 * kk][1]),
                           pack_bf16(s[i][2 * kk][2], s[i][2 * kk][3]),
                           pack_bf16(s[i][2 * kk + 1][0], s[i][2 * kk + 1][1]),
@@ -324,9 +341,15 @@ __global__ __launch_bounds__(256, 3) void k_attention(
   for (int i = 0; i < QT; ++i) {
     const int q = q0 + i * 16 + fr;
     const float l = ol[i][0];
+    if (STATS) {   // before the `continue`: every lane takes part in the exchange
+      // the four lane rows of a query hold 16 keys of a tile each
+      float lf = lsum[i][0] + lsum[i][1];
+      lf += __shfl_xor(lf, 16);
+      lf += __shfl_xor(lf, 32);
+      if (q < T && fg == 0)
+        lse[((int64_t)b * H + h) * Tp + q] = __builtin_amdgcn_logf(lf) - negm[i];
+    }
     if (q >= T) continue;
-    if (STATS && fg == 0)
-      lse[((int64_t)b * H + h) * Tp + q] = __builtin_amdgcn_logf(l) - negm[i];
     const float inv = l > 0.f ? 1.f / l : 0.f;
     bf16_t* op = out + ((int64_t)b * T + q) * (int64_t)H * HD + (int64_t)h * HD;
 #pragma unroll
