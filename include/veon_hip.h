@@ -1118,6 +1118,51 @@ int veon_occ_align_bwd(const float *feat, const int64_t *feat_strides, int C, in
                        const int *order, const int *seg_start, int M, const int *occ_rows,
                        float *rows, float *grad, void *stream);
 
+/* ======== depth_loss.hip ============================================================ */
+
+/* Depth pre-training loss, VeonDepthPretrain.forward_train
+ * (detectors/veon_depth_pretrain.py:128-154): downsample_depth of the prediction (by sp)
+ * and of the LiDAR depth (by sg), the mean-absolute-error statistic and
+ * get_depth_loss_own(zoe, ce) (necks/view_transformer_raw.py:497-535), forward and
+ * backward, with no read-back, no atomics and no memset.  depth (BN,Hp,Wp) and gt_depth
+ * (BN,Hg,Wg) fp32 contiguous; sp, sg in {1, 2, 4, 8, 16}, each dividing its map, and
+ * Hp/sp = Hg/sg = h, Wp/sp = Wg/sg = w, otherwise VEON_ERR_BAD_ARG.  A row is one of the
+ * BN*h*w output pixels (at most 2^31 - 1); 1 <= D <= 32767; rec is 16-byte aligned.
+ *
+ * veon_depth_loss_rows writes one record of VEON_DEPTH_LOSS_REC floats per row, with
+ * d / t the block-min of the row's prediction / label block, zeros read as 1e5:
+ *   [0] g = log(d + 1e-7) - log(t + 1e-7)      [4] d
+ *   [1] |d - t|                                [5] t
+ *   [2] two-hot BCE of the row, 0 unless fg    [6] d [2] / d d, 0 unless fg
+ *   [3] int: bit 0 valid (t < 9225),           [7] int: bits 0-7 the winning pixel
+ *       bit 1 fg (label bin k* < D)                dy*sp + dx (first on ties), bit 8 set
+ *                                                  when it was a zero, bits 16-30 k*
+ * k* = argmax_k -|min(t, 500) - c_k| (first on ties) over the D+1 centres
+ * c_k = k*step + (lo + step/2) of veon_two_hot_depth; [2] = -log p_k* - sum_{k<D, k!=k*}
+ * log(1 - p_k), logs clamped at -100, p the softmax of -gamma*|d - c_k| clamped at -16.
+ * [6] is autograd's: the clamp is straight-through (slope -gamma*sign(d - c_k) on every
+ * bin) and binary_cross_entropy's backward is (p - y)/max(p(1 - p), 1e-12).
+ *
+ * veon_depth_loss_reduce (one workgroup, fixed-order fp64 sums) writes
+ *   out[0] = min(sqrt(Dg), 2), Dg = var(g) + 0.15 mean(g)^2 over the n valid rows
+ *            (unbiased; n < 2 gives NaN as the torch formulation does)
+ *   out[1] = 0.05 * sum of [2] / max(1, n_fg)      out[2] = mean [1] over the valid rows
+ *   coef[0..7] = mean, a = 1/((n-1) sqrt Dg), b = 0.15 mean/(n sqrt Dg) (a = b = 0 when
+ *            clipped), 0.05/max(1, n_fg), n, n_fg, sqrt Dg, 1.0 when clipped.
+ *
+ * veon_depth_loss_bwd stores EVERY element of grad (BN,Hp,Wp): on a row's winning pixel,
+ * unless that pixel was a zero,
+ *   *g_zoe * ((g - mean) a + b)/(d + 1e-7)  [valid rows]  +  *g_ce * coef[3] * [6]  [fg]
+ * and 0 elsewhere.  g_zoe / g_ce: device scalars, NULL = that loss has no gradient. */
+#define VEON_DEPTH_LOSS_REC 8
+int veon_depth_loss_rows(int BN, int Hp, int Wp, int sp, int Hg, int Wg, int sg, int D,
+                         float lo, float step, float gamma, const float *depth,
+                         const float *gt_depth, float *rec, void *stream);
+int veon_depth_loss_reduce(int64_t rows, const float *rec, float *out, float *coef,
+                           void *stream);
+int veon_depth_loss_bwd(int BN, int Hp, int Wp, int sp, const float *rec, const float *coef,
+                        const float *g_zoe, const float *g_ce, float *grad, void *stream);
+
 /* ======== memory.hip ================================================================ */
 
 /* Physically contiguous device memory (hipExtMallocWithFlags +
