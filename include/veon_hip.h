@@ -1163,6 +1163,71 @@ int veon_depth_loss_reduce(int64_t rows, const float *rec, float *out, float *co
 int veon_depth_loss_bwd(int BN, int Hp, int Wp, int sp, const float *rec, const float *coef,
                         const float *g_zoe, const float *g_ce, float *grad, void *stream);
 
+/* ======== occ_bin_loss.hip ========================================================== */
+
+/* The occupancy term of the training loss, BCE_BinOcc_Loss
+ * (loss/occ_loss_utils/occ3d_nuscenes.py:200-212) on the trilinearly upsampled bin_occ
+ * (san_in_veon_temporal.py:202-210), from the LOW-resolution logits, forward and backward,
+ * with no read-back, no atomics and no memset; the upsampled logits are never stored.
+ * logits (B,2,zi,yi,xi) fp32 through five ELEMENT strides {b, c, z, y, x} (all >= 0);
+ * labels (B,Xo,Yo,Zo) uint8 contiguous: output voxel (zo, yo, xo) has label
+ * labels[b][xo][yo][zo]; class_weights: 2 floats (w_0, w_1) on the device.  B*Zo*Yo*Xo is
+ * at most 2^31 - 1, otherwise VEON_ERR_BAD_ARG.
+ *
+ * With up = trilinear(logits, align_corners=False) at the output voxel (the index rule of
+ * occ_align_loss.hip and occ_retrieval.hip), t = 0 for label < free_index and 1 for
+ * label >= free_index, and voxels with label == ignore_index not counted:
+ *   nll   = logsumexp(up_0, up_1) - up_t   (the maximum subtracted first)
+ *   loss  = sum w_t nll / sum w_t          over the counted voxels
+ * veon_occ_bin_loss_fwd writes
+ *   coef[n] = w_t (p_0 - [t == 0]) = d (w_t nll) / d up_0, 0 where ignored, one float per
+ *             output voxel in LABEL order (n = ((b Xo + xo) Yo + yo) Zo + zo); the
+ *             derivative with respect to up_1 is -coef[n]
+ *   out[0]  = loss (NaN when every voxel is ignored, as torch)
+ *   out[1]  = 1 / sum w_t (0 when every voxel is ignored: the gradient is then all zeros)
+ * `workspace`: veon_occ_bin_loss_workspace_bytes(B, Zo, Yo, Xo) bytes (host-only; -1:
+ * unsupported size), 8-byte aligned: per-workgroup fp64 partial sums, added in a fixed
+ * order; too small gives VEON_ERR_WORKSPACE.  Repeated calls are bit-identical.
+ *
+ * veon_occ_bin_loss_bwd, for the grid (2 zi, 2 yi, 2 xi) only: stores EVERY element of
+ * grad (B,2,zi,yi,xi) fp32 contiguous,
+ *   grad[b][0][i] = *gout * out[1] * sum over the outputs o that read i of coef[o] *
+ *                   (product of the three axis weights with which o reads i),
+ *   grad[b][1][i] = -grad[b][0][i],
+ * the outputs visited in a fixed order ([2i-1, 2i+2] per axis, clipped to the grid; the
+ * weights come from the forward's own index rule, clamped borders included).  coef and out
+ * as the forward wrote them for that grid; gout: the upstream gradient, a device scalar. */
+int64_t veon_occ_bin_loss_workspace_bytes(int B, int Zo, int Yo, int Xo);
+int veon_occ_bin_loss_fwd(const float *logits, const int64_t *logit_strides, int B, int zi,
+                          int yi, int xi, int Zo, int Yo, int Xo,
+                          const unsigned char *labels, const float *class_weights,
+                          int ignore_index, int free_index, float *coef, void *workspace,
+                          int64_t workspace_bytes, float *out, void *stream);
+int veon_occ_bin_loss_bwd(const float *coef, const float *out, const float *gout, int B,
+                          int zi, int yi, int xi, float *grad, void *stream);
+
+/* ======== volume_handover.hip ======================================================= */
+
+/* Hand-over between the padded half rows the prediction heads train on and the fp32
+ * channels-last tensors of the feature-alignment loss.
+ *
+ * veon_volume_unpack_cl_f32: interior of a padded half grid [B][Z+2][Y+2][X+2][Cp] -> out
+ * (B,Z,Y,X,C) fp32 contiguous (16-byte aligned), the first C <= Cp channels; Cp % 4 == 0.
+ *
+ * veon_volume_sigm_bwd_pack_cl: backward of f = sigmoid(pre) - 0.5 fused with the pack.
+ * grad: fp32 (B,Z,Y,X,C) through four ELEMENT strides {b, z, y, x} (all >= 0, x stride
+ * >= C), channel stride 1; f_storage / out_storage: whole storages of padded half grids
+ * of C channels, guard_rows = veon_conv3d_guard_rows(Y, X) rows before and after the
+ * padded rows (anything else is VEON_ERR_BAD_ARG), C % 4 == 0, not aliased.  Every row
+ * of out_storage is stored: d pre = grad * (0.25 - f^2) rounded to half on interior
+ * rows, ZERO on halo and guard rows (no memset needed). */
+int veon_volume_unpack_cl_f32(const void *padded, float *out, int B, int Cp, int C, int Z,
+                              int Y, int X, void *stream);
+int veon_volume_sigm_bwd_pack_cl(const float *grad, const int64_t *grad_strides,
+                                 const void *f_storage, void *out_storage,
+                                 int64_t guard_rows, int B, int C, int Z, int Y, int X,
+                                 void *stream);
+
 /* ======== memory.hip ================================================================ */
 
 /* Physically contiguous device memory (hipExtMallocWithFlags +

@@ -107,6 +107,41 @@ def unpack(vol, out=None):
     return out
 
 
+def unpack_cl(vol, channels=None):
+    """PaddedVolume -> contiguous fp32 (B, Z, Y, X, C) of its first ``channels`` channels
+    (all by default): channels-last, no transpose.  Permuted to (B, C, Z, Y, X) its channel
+    stride is 1, which is what ``align_loss.voxel_cosine`` reads without a copy."""
+    dev = _lib.require_device(vol.storage)
+    _lib.require_half(vol.rows)
+    B, Cp, Z, Y, X = vol.shape
+    C = Cp if channels is None else int(channels)
+    out = torch.empty((B, Z, Y, X, C), dtype=torch.float32, device=dev)
+    _lib.launch('veon_volume_unpack_cl_f32', dev, vol.rows, out, B, Cp, C, Z, Y, X)
+    return out
+
+
+def sigm_bwd_pack_cl(grad, f, out=None):
+    """Backward of ``f = sigmoid(pre) - 0.5`` fused with the pack: ``grad`` fp32
+    (B, C, Z, Y, X) with channel stride 1 (any outer strides), ``f`` the stored half output
+    (PaddedVolume) -> d pre = grad * (0.25 - f^2) as a PaddedVolume whose every row is
+    stored, halo and guard rows as zeros (``out``: an existing volume to overwrite)."""
+    import ctypes
+    dev = _lib.require_device(grad, f.storage)
+    _lib.require_half(f.storage)
+    B, C, Z, Y, X = f.shape
+    if tuple(grad.shape) != f.shape or grad.dtype != torch.float32 or grad.stride(1) != 1:
+        raise _lib.VeonHipError('sigm_bwd_pack_cl takes a channels-last fp32 gradient of %s, '
+                                'got %s %s with strides %s' % (f.shape, grad.dtype,
+                                                               tuple(grad.shape), grad.stride()))
+    if out is None:
+        out = PaddedVolume.from_storage(torch.empty_like(f.storage), f.shape)
+    assert out.shape == f.shape and out is not f
+    st = (ctypes.c_int64 * 4)(grad.stride(0), grad.stride(2), grad.stride(3), grad.stride(4))
+    _lib.launch('veon_volume_sigm_bwd_pack_cl', dev, grad, ctypes.cast(st, ctypes.c_void_p),
+                f.storage, out.storage, f.guard, B, C, Z, Y, X)
+    return out
+
+
 def pack_weight(w):
     """nn.Conv3d weight (Cout,Cin,3,3,3) -> bf16 [Cout][3][3][3][Cin]."""
     assert w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3)

@@ -209,14 +209,6 @@ __global__ __launch_bounds__(256) void k_align_rows(
   }
 }
 
-// weight with which output index o feeds low-resolution index j along one axis
-__device__ __forceinline__ float axis_weight(int o, int out_size, int j, float scale,
-                                             int in_size) {
-  if (o < 0 || o >= out_size) return 0.f;
-  const Axis a = source(o, scale, in_size);
-  return (a.i0 == j ? a.l0 : 0.f) + (a.i1 == j ? a.l1 : 0.f);
-}
-
 // Pass B (2x per axis).  grad: (zi, yi, xi, C) contiguous, every element stored once.
 template <int W, int K>
 __global__ __launch_bounds__(256) void k_align_gather(

@@ -33,6 +33,16 @@ __device__ __forceinline__ Axis source(int dst, float scale, int in_size) {
   return a;
 }
 
+// Weight with which output index o feeds low-resolution index j along one axis (0 for an
+// o outside the grid): the transpose of `source`, for the gather-form backwards.  At a
+// clamped border both taps land on the same index and their weights add.
+__device__ __forceinline__ float axis_weight(int o, int out_size, int j, float scale,
+                                             int in_size) {
+  if (o < 0 || o >= out_size) return 0.f;
+  const Axis a = source(o, scale, in_size);
+  return (a.i0 == j ? a.l0 : 0.f) + (a.i1 == j ? a.l1 : 0.f);
+}
+
 // v[0..7] = corners (z0y0x0, z0y0x1, z0y1x0, z0y1x1, z1y0x0, ...): ATen's nested blend
 __device__ __forceinline__ float blend(const float* v, const Axis& az, const Axis& ay,
                                        const Axis& ax) {

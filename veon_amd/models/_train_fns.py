@@ -9,8 +9,9 @@ those ``needs_input_grad`` asks for are computed.  In the fp16 flavour every gra
 between two kernels is rounded to fp16: loss scaling is the caller's business.
 """
 import torch
+import torch.nn.functional as F
 
-from .. import vit_ops
+from .. import conv3d_ops, vit_ops
 
 LORA_PAD = 64   # the rank is zero-padded to the GEMM's and the weight gradient's tile width
 
@@ -180,3 +181,50 @@ class _LoRALinearTrainFn(torch.autograd.Function):
         if need[4]:
             dlb = (vit_ops.linear_wgrad(dy, u)[:, :r] * s).to(lora_b.dtype)
         return da, dw, db, dla, dlb, None
+
+
+# ------------------------------------------------- padded volumes (storage tensors)
+# The differentiable values of the native training paths on volumes are the STORAGE tensors
+# of PaddedVolumes (half, guard rows included), as in ``_ResBlockTrainFn``; ``shape`` is the
+# (B, C, Z, Y, X) of the volume a storage tensor holds.
+def _rows_linear(xs, shape, w, b):
+    """1x1x1 conv as ``_LinearTrainFn`` on the rows of the padded grid -> storage.  The
+    halo rows of the result hold the bias (zeros without one); the guard rows are zero."""
+    guard = (xs.shape[0] - conv3d_ops.PaddedVolume.rows_of(shape)) // 2
+    y = _LinearTrainFn.apply(xs[guard:xs.shape[0] - guard], w.view(w.shape[0], -1), b)
+    return F.pad(y, (0, 0, guard, guard))
+
+
+class _BNReLUTrainFn(torch.autograd.Function):
+    """Train-mode BatchNorm3d + ReLU of a stored volume ``ys`` with a ZERO halo.  ``bias``
+    is the bias of the 1x1x1 conv that produced ``ys`` WITHOUT adding it (so the halo
+    stayed zero): a per-channel constant ahead of train-mode BN cancels in the output and
+    has zero gradient, so it only enters the running mean (None: the conv has no bias)."""
+
+    @staticmethod
+    def forward(ctx, ys, g, b, bias, shape, bn):
+        y = conv3d_ops.PaddedVolume.from_storage(ys, shape)
+        B, C, Z, Y, X = shape
+        n = B * Z * Y * X
+        mean, var, rstd = conv3d_ops.bn_batch_stats(conv3d_ops.bn_sums(y), n, bn.eps)
+        conv3d_ops.bn_update_running(
+            bn, mean if bias is None else mean + bias.detach().double(), var, n)
+        scale = g.detach().double() * rstd
+        shift = b.detach().double() - mean * scale
+        a = conv3d_ops.bn_apply(y, scale.float(), shift.float(), relu=True)
+        ctx.shape = tuple(shape)
+        ctx.save_for_backward(ys, a.storage, mean.float(), rstd.float(), g, bias)
+        return a.storage
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        ys, as_, mu, r, g, bias = ctx.saved_tensors
+        B, C, Z, Y, X = ctx.shape
+        vol = conv3d_ops.PaddedVolume.from_storage
+        y, a, da = vol(ys, ctx.shape), vol(as_, ctx.shape), vol(dout.contiguous(), ctx.shape)
+        n = B * Z * Y * X
+        s = conv3d_ops.bn_bwd_sums(da, a, y, mu, r)
+        dy = conv3d_ops.bn_bwd_apply(da, a, y, *conv3d_ops.bn_bwd_coefficients(s, n, g, mu, r))
+        return (dy.storage, s[1].to(g.dtype), s[0].to(g.dtype),
+                torch.zeros_like(bias) if bias is not None and ctx.needs_input_grad[3] else None, None, None)

@@ -17,13 +17,17 @@ epilogue, and the result is unpacked once at the end.  Training and CPU tensors
 take the plain PyTorch formulation (the definition of the module), unless
 ``ResBlock3D.hip_train`` is set: then a training-mode block on a ROCm volume trains
 on the same padded grid (csrc/conv3d_train.hip: train-mode BatchNorm passes, data
-gradient through the forward kernel, MFMA weight gradient).
+gradient through the forward kernel, MFMA weight gradient).  ``_PredHead3D.hip_train``
+is the same switch for the two prediction heads: their 1x1x1 convs train as GEMMs on the
+rows of that grid, straight from the body's storage when both are native.
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
-from ... import conv3d_ops, vit_ops
+from ... import _lib, conv3d_ops, vit_ops
 from .._native_cache import NativeCacheMixin
+from .._train_fns import LORA_PAD, _BNReLUTrainFn, _half_weight, _rows_linear
 from ... import half as _half
 
 
@@ -93,15 +97,130 @@ def _pointwise(vol, cm, out_channels=None, epilogue=None):
     return out
 
 
+def _stage_train(cm, xs, shape):
+    """A 1x1x1 ConvModule3d (conv -> train-mode BN -> ReLU) on the storage ``xs`` of a
+    PaddedVolume of ``shape`` -> (storage, shape).  The GEMM runs without the conv's bias,
+    so the halo stays zero; the bias only enters the running mean (``_BNReLUTrainFn``)."""
+    ys = _rows_linear(xs, shape, cm.conv.weight, None)
+    oshape = (shape[0], cm.conv.out_channels) + tuple(shape[2:])
+    return _BNReLUTrainFn.apply(ys, cm.bn.weight, cm.bn.bias, cm.conv.bias, oshape,
+                                cm.bn), oshape
+
+
+class _SigmTailFn(torch.autograd.Function):
+    """The last conv of ``PredHead3DSem`` with its ``sigmoid - 0.5`` for training: one
+    GEMM with the ``EPI_AFFINE_SIGM`` epilogue on the storage ``xs`` (the halo stays zero:
+    sigmoid(0) - 0.5 = 0), handed over as an fp32 (B, C, z, y, x) tensor whose channel
+    stride is 1 (what ``voxel_cosine`` reads without a copy).  Saved: the input and the
+    stored half output f, which is all the activation's backward needs:
+    d pre = d f (0.25 - f^2), fused with the pack of the channels-last gradient that
+    ``voxel_cosine``'s backward returns (any other layout is made channels-last first)."""
+
+    @staticmethod
+    def forward(ctx, xs, w, shape):
+        x = conv3d_ops.PaddedVolume.from_storage(xs, shape)
+        B, _, Z, Y, X = shape
+        f = conv3d_ops.PaddedVolume(B, w.shape[0], Z, Y, X, xs.device)
+        vit_ops.linear(x.rows, _half_weight(w.view(w.shape[0], -1)), None,
+                       vit_ops.EPI_AFFINE_SIGM, out=f.rows)
+        ctx.shape = tuple(shape)
+        ctx.save_for_backward(xs, f.storage, w)
+        return conv3d_ops.unpack_cl(f).permute(0, 4, 1, 2, 3)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        xs, fs, w = ctx.saved_tensors
+        B, _, Z, Y, X = ctx.shape
+        vol = conv3d_ops.PaddedVolume.from_storage
+        x, f = vol(xs, ctx.shape), vol(fs, (B, w.shape[0], Z, Y, X))
+        if g.dtype != torch.float32 or g.stride(1) != 1:
+            g = g.float().permute(0, 2, 3, 4, 1).contiguous().permute(0, 4, 1, 2, 3)
+        dpre = conv3d_ops.sigm_bwd_pack_cl(g, f)
+        need_x, need_w = ctx.needs_input_grad[:2]
+        dw = vit_ops.linear_wgrad(dpre.rows, x.rows).view_as(w).to(w.dtype) if need_w else None
+        dxs = None
+        if need_x:
+            dx = x.like()
+            vit_ops.linear(dpre.rows, _half_weight(w.view(w.shape[0], -1), transpose=True),
+                           out=dx.rows)
+            dxs = dx.storage
+        return dxs, dw, None
+
+
 class _PredHead3D(nn.Module):
     """Shared machinery of the two prediction heads: a chain of 1x1x1
     ConvModules.  On a PaddedVolume (or a ROCm fp32 volume at inference) the
-    chain runs as GEMMs on the channels-last rows."""
+    chain runs as GEMMs on the channels-last rows.
+
+    ``hip_train`` (class attribute, default False): opt-in native TRAINING path, as on
+    ``ResBlock3D``.  When set, a training-mode head with grad enabled whose widths the
+    kernels support runs its chain under autograd on the storage tensor of a PaddedVolume
+    (``_rows_linear`` + ``_BNReLUTrainFn`` per conv -> BN -> ReLU stage); its input is a
+    ROCm fp32 volume, which it packs, or the ``(storage, shape)`` pair that
+    ``run_blocks(..., return_storage=True)`` hands over.  Parameter gradients are fp32 in
+    the parameters' own layout.  Anything else takes the torch definition.  Hooks on the
+    ConvModules do not fire on the native path."""
 
     _names = ()
+    hip_train = False
+    # whether ``_train_native`` zero-pads a last conv narrower than 64 outputs to 64 rows
+    # (PredHead3DOcc); a head that does not needs every output width a multiple of 64
+    _pads_narrow_tail = False
 
     def _chain(self):
         return [getattr(self, n) for n in self._names]
+
+    def _train_structure_ok(self):
+        """The part of ``_hip_train_ok`` that depends on the module alone: 1x1x1 stride-1
+        fp32 convs, every GEMM width a multiple of 64 (in a head that pads it,
+        ``_pads_narrow_tail``, a last conv without BN may have at most 8 outputs instead:
+        it is zero-padded to 64 rows), BN in training mode with affine
+        parameters and running statistics at a width the sums kernel supports."""
+        chain = self._chain()
+        for cm in chain:
+            c = cm.conv
+            if c.kernel_size != (1, 1, 1) or c.stride != (1, 1, 1) or c.padding != (0, 0, 0) \
+                    or c.weight.dtype != torch.float32 or c.in_channels % 64:
+                return False
+            if cm.bn is None:
+                if cm is not chain[-1] or cm.activate is not None or c.bias is not None:
+                    return False
+                if c.out_channels % 64 and not (self._pads_narrow_tail
+                                                and c.out_channels <= 8):
+                    return False
+                continue
+            bn = cm.bn
+            if c.out_channels % 64 or cm.activate is None or not (
+                    bn.training and bn.affine and bn.track_running_stats
+                    and bn.running_mean is not None):
+                return False
+            if _lib.lib().veon_bn3d_sums_workspace_bytes(c.out_channels) < 0:
+                return False
+        return True
+
+    def _hip_train_ok(self, x):
+        """The native training path's own test: the switch, training mode, grad enabled,
+        a ROCm fp32 volume or a (storage, shape) pair, and ``_train_structure_ok``."""
+        if not (self.hip_train and self.training and torch.is_grad_enabled()):
+            return False
+        if isinstance(x, tuple):
+            xs = x[0]
+            ok = torch.is_tensor(xs) and xs.is_cuda and xs.dim() == 2 and xs.dtype == _half.dtype()
+        else:
+            ok = torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5
+        return bool(ok) and self._train_structure_ok()
+
+    @staticmethod
+    def _train_input(x):
+        """-> (storage, shape) of the head's input: handed over, or packed here."""
+        if isinstance(x, tuple):
+            return x[0], tuple(int(v) for v in x[1])
+        return _PackFn.apply(x), tuple(x.shape)
+
+    @staticmethod
+    def _torch_input(x):
+        return _UnpackFn.apply(*x) if isinstance(x, tuple) else x
 
     def _hip_ok(self, x):
         if not all(cm.conv.in_channels % 64 == 0 for cm in self._chain()):
@@ -134,6 +253,7 @@ class PredHead3DOcc(_PredHead3D):
     BN, ReLU; 1x1x1 conv C/4 -> channels_out."""
 
     _names = ('occ_conv1', 'occ_conv2')
+    _pads_narrow_tail = True
 
     def __init__(self, channels_in, channels_out, stride=1, use_checkpoint=False):
         super().__init__()
@@ -145,7 +265,24 @@ class PredHead3DOcc(_PredHead3D):
         self.use_checkpoint = use_checkpoint
 
     def forward(self, x):
-        return self._run(x)
+        if self._hip_train_ok(x):
+            return self._train_native(*self._train_input(x))
+        return self._run(self._torch_input(x))
+
+    def _train_native(self, xs, shape):
+        """The last conv's weight is zero-padded to 64 output rows (as the LoRA branches pad
+        their rank; autograd returns the parameter's rows of the padded gradient); its
+        first 8 channels leave through the ordinary unpack of an 8-channel volume."""
+        a, s1 = _stage_train(self.occ_conv1, xs, shape)
+        w = self.occ_conv2.conv.weight
+        cout = w.shape[0]
+        if cout % 64:
+            w = F.pad(w.view(cout, -1), (0, 0, 0, LORA_PAD - cout))
+        ys = _rows_linear(a, s1, w, None)
+        if cout % 64 == 0:
+            return _UnpackFn.apply(ys, (s1[0], cout) + tuple(s1[2:]))
+        out = _UnpackFn.apply(ys[:, :8].contiguous(), (s1[0], 8) + tuple(s1[2:]))
+        return out[:, :cout]
 
 
 class PredHead3DSem(_PredHead3D):
@@ -168,6 +305,12 @@ class PredHead3DSem(_PredHead3D):
         """``return_volume`` (MFMA path only): keep the result -- sigmoid - 0.5
         applied in place on the bf16 rows -- as the PaddedVolume that
         ``semantic_inference_3d_fused`` consumes."""
+        if not return_volume and self._hip_train_ok(x):
+            xs, shape = self._train_input(x)
+            xs, shape = _stage_train(self.occ_conv1, xs, shape)
+            xs, shape = _stage_train(self.occ_conv2, xs, shape)
+            return _SigmTailFn.apply(xs, self.occ_conv3.conv.weight, shape)
+        x = self._torch_input(x)
         if return_volume and self._hip_ok(x):
             # sigmoid(x) - 0.5 = tanh(x/2)/2 in the last GEMM's epilogue (fp32, before
             # the bf16 rounding; halo rows are never read)
@@ -379,10 +522,13 @@ class _UnpackFn(torch.autograd.Function):
         return conv3d_ops.pack(g).storage, None
 
 
-def run_blocks(blocks, x):
+def run_blocks(blocks, x, return_storage=False):
     """``blocks`` (ResBlock3D) applied in order to the fp32 volume ``x``.  A run of
     consecutive blocks that take the native training path (``ResBlock3D.hip_train``) is
-    packed once and unpacked once; every other block is called as it is."""
+    packed once and unpacked once; every other block is called as it is.
+    ``return_storage``: when the LAST block belongs to a native run, that run is not
+    unpacked and the result is the pair ``(storage, shape)`` of its PaddedVolume (what the
+    prediction heads' native training path takes); otherwise the fp32 volume as usual."""
     blocks = list(blocks)
     i = 0
     while i < len(blocks):
@@ -395,8 +541,19 @@ def run_blocks(blocks, x):
         while i < len(blocks) and blocks[i]._hip_train_ok(x):
             xs = blocks[i]._train_native(xs, shape)
             i += 1
+        if return_storage and i == len(blocks):
+            return xs, shape
         x = _UnpackFn.apply(xs, shape)
     return x
+
+
+def run_blocks_into_heads(blocks, x, heads):
+    """The LAST run of a decoder's blocks ahead of its prediction ``heads``: when every
+    head takes its native training path on ``x``, a trailing run of native blocks hands its
+    storage over (``run_blocks(..., return_storage=True)``: no unpack -> pack pair, one
+    saved input for all heads); otherwise ``run_blocks`` as it is."""
+    to_heads = torch.is_tensor(x) and all(h._hip_train_ok(x) for h in heads)
+    return run_blocks(blocks, x, return_storage=to_heads)
 
 
 class ResBlock3D(nn.Module):

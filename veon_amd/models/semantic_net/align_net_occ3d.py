@@ -25,7 +25,7 @@ import torch.nn as nn
 
 from ... import conv3d_ops
 from .align_net_body import (AlignBody3D, PredHead3DOcc, PredHead3DSem, ResBlock3D,
-                              run_blocks)
+                              run_blocks, run_blocks_into_heads)
 from .fusion_layers import build_fusion_layer_lift
 from .temporal_fusion import TemporalFusionMultiFrame
 
@@ -194,7 +194,13 @@ class AlignNetOcc3D(nn.Module):
             while stop < len(blocks) and stop not in self.fusion_map and not (
                     stop == self.tf_layers and occ_feat_prevs is not None):
                 stop += 1
-            x = run_blocks(blocks[idx:stop], x)
+            # the last run hands its storage straight to two native heads: no unpack ->
+            # pack pair in between, one saved input for both
+            if stop == len(blocks):
+                x = run_blocks_into_heads(blocks[idx:stop], x,
+                                          (self.occupancy_pred, self.feat_pred))
+            else:
+                x = run_blocks(blocks[idx:stop], x)
             idx = stop
         return {'bin_occ': self.occupancy_pred(x), 'feat_occ': self.feat_pred(x)}
 

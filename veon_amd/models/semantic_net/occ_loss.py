@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ...align_loss import voxel_cosine
+from ...occ_bin_loss import bin_occ_loss
 from ...retrieval import retrieve_points
 
 
@@ -235,13 +236,19 @@ class OccLossFB(nn.Module):
     inputs.  Every ``*_weight`` of ``loss_weight_cfg`` is also an attribute.
     ``class_weights`` (for the semantic CE term, which ``loss_voxel`` never calls) is
     1 / log(frequency + 0.001) when ``class_frequencies`` is given -- the dataset
-    statistic is not part of this package -- and uniform otherwise."""
+    statistic is not part of this package -- and uniform otherwise.
+
+    ``hip_train`` (keyword and attribute, default False): opt-in native occupancy term.
+    When set and ``bin_occ`` is an fp32 tensor on a ROCm device, ``loss_voxel`` takes it
+    from ``occ_bin_loss.bin_occ_loss`` (csrc/occ_bin_loss.hip: upsampling and cross entropy
+    fused in both directions, nothing read back); anything else runs the torch sequence."""
 
     def __init__(self, out_channel=18, loss_weight_cfg=None, empty_idx=17, ignore_idx=255,
                  balance_cls_weight=True, grid_config=None, mode='nuscenes',
                  high_conf_thr=0.985, stage2_start=2, priority=None, ov_class_number=17,
-                 class_frequencies=None):
+                 class_frequencies=None, hip_train=False):
         super().__init__()
+        self.hip_train = bool(hip_train)
         if mode not in ('semkitti', 'nuscenes'):
             raise ValueError('unknown mode %r' % (mode,))
         self.loss_weight_cfg = dict(_DEFAULT_WEIGHTS) if loss_weight_cfg is None else loss_weight_cfg
@@ -268,6 +275,19 @@ class OccLossFB(nn.Module):
     def epoch(self, value):
         self.proj2dto3dloss.epoch = value
 
+    def _bin_weights_on(self, device):
+        """``bin_class_weights`` as fp32 on ``device``, copied once per device and per value
+        of the attribute (keyed on the tensor's storage and version counter, so no element
+        is read: nothing synchronises, and a captured step stays capturable; the torch
+        sequence copies the weights every step)."""
+        w = self.bin_class_weights
+        key = (str(device), w.data_ptr(), w._version, str(w.device))
+        cache = self.__dict__.setdefault('_bin_weights_dev', {})
+        if key not in cache:
+            cache.clear()
+            cache[key] = w.detach().to(device=device, dtype=torch.float32).contiguous()
+        return cache[key]
+
     def masked_labels(self, voxel_semantics, mask_camera):
         """The labels with ``ignore_idx`` where no camera sees the voxel, in a copy (the
         reference overwrites the caller's tensor)."""
@@ -285,12 +305,19 @@ class OccLossFB(nn.Module):
             class_reflection=meta_info['class_reflection'],
             ov_classifier_weight=meta_info['ov_classifier_weight'],
             class_num=self.out_channel, occ_size=occ_size)
-        # 2 channels, 5 MB at the VEON grid: upsampled in torch, (B, 2, X, Y, Z) as the labels
-        bin_up = F.interpolate(semantic_results['bin_occ'].float(), size=occ_size,
-                               mode='trilinear', align_corners=False).permute(0, 1, 4, 3, 2)
-        value['loss_binocc'] = self.bin_occ_loss(bin_up, target_voxels,
-                                                 self.bin_class_weights.to(bin_up),
-                                                 ignore_index=self.ignore_idx)
+        bin_low = semantic_results['bin_occ']
+        if self.hip_train and bin_low.is_cuda and bin_low.dtype == torch.float32:
+            value['loss_binocc'] = bin_occ_loss(
+                bin_low, target_voxels, self._bin_weights_on(bin_low.device), occ_size,
+                ignore_index=self.ignore_idx)
+        else:
+            # 2 channels, 5 MB at the VEON grid: upsampled in torch, (B, 2, X, Y, Z) as the
+            # labels
+            bin_up = F.interpolate(bin_low.float(), size=occ_size, mode='trilinear',
+                                   align_corners=False).permute(0, 1, 4, 3, 2)
+            value['loss_binocc'] = self.bin_occ_loss(bin_up, target_voxels,
+                                                     self.bin_class_weights.to(bin_up),
+                                                     ignore_index=self.ignore_idx)
         n_open, n_all = self.ov_class_number, self.out_channel - 1
         return {'%s_%s' % (stem, tag): getattr(self, weight) * value[stem]
                 for stem, weight, present in _TERMS if present(n_open, n_all)}

@@ -30,7 +30,7 @@ import torch.nn.functional as F
 
 from ... import conv3d_ops, vit_ops
 from .._native_cache import NativeCacheMixin
-from .._train_fns import _LinearTrainFn
+from .._train_fns import _BNReLUTrainFn, _rows_linear
 from .align_net_body import (ConvModule3d, _PackFn, _UnpackFn, conv_module_train,
                              conv_module_train_ok)
 from ... import half as _half
@@ -67,15 +67,8 @@ def _cat(vols):
 # ------------------------------------------------- native training (storage tensors)
 # The differentiable values of the native training path are the STORAGE tensors of
 # PaddedVolumes (half, guard rows included), as in ``_ResBlockTrainFn``; ``shape`` is the
-# (B, C, Z, Y, X) of the volume a storage tensor holds.
-def _rows_linear(xs, shape, w, b):
-    """1x1x1 conv as ``_LinearTrainFn`` on the rows of the padded grid -> storage.  The
-    halo rows of the result hold the bias (zeros without one); the guard rows are zero."""
-    guard = (xs.shape[0] - conv3d_ops.PaddedVolume.rows_of(shape)) // 2
-    y = _LinearTrainFn.apply(xs[guard:xs.shape[0] - guard], w.view(w.shape[0], -1), b)
-    return F.pad(y, (0, 0, guard, guard))
-
-
+# (B, C, Z, Y, X) of the volume a storage tensor holds.  ``_rows_linear`` and
+# ``_BNReLUTrainFn`` live in ``models/_train_fns.py`` (the prediction heads share them).
 class _ConvBiasTrainFn(torch.autograd.Function):
     """3x3x3 conv (+ bias) on padded rows, no norm, no activation: the stored output is
     the pre-activation.  Backward: bias gradient (``colsum``), MFMA weight gradient, data
@@ -119,40 +112,6 @@ class _GeluVolFn(torch.autograd.Function):
     def backward(ctx, dh):
         ys, = ctx.saved_tensors
         return vit_ops.gelu_bwd(dh.contiguous(), ys)
-
-
-class _BNReLUTrainFn(torch.autograd.Function):
-    """Train-mode BatchNorm3d + ReLU of a stored volume ``ys`` with a ZERO halo.  ``bias``
-    is the bias of the 1x1x1 conv that produced ``ys`` WITHOUT adding it (so the halo
-    stayed zero): a per-channel constant ahead of train-mode BN cancels in the output and
-    has zero gradient, so it only enters the running mean."""
-
-    @staticmethod
-    def forward(ctx, ys, g, b, bias, shape, bn):
-        y = conv3d_ops.PaddedVolume.from_storage(ys, shape)
-        B, C, Z, Y, X = shape
-        n = B * Z * Y * X
-        mean, var, rstd = conv3d_ops.bn_batch_stats(conv3d_ops.bn_sums(y), n, bn.eps)
-        conv3d_ops.bn_update_running(bn, mean + bias.detach().double(), var, n)
-        scale = g.detach().double() * rstd
-        shift = b.detach().double() - mean * scale
-        a = conv3d_ops.bn_apply(y, scale.float(), shift.float(), relu=True)
-        ctx.shape = tuple(shape)
-        ctx.save_for_backward(ys, a.storage, mean.float(), rstd.float(), g, bias)
-        return a.storage
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dout):
-        ys, as_, mu, r, g, bias = ctx.saved_tensors
-        B, C, Z, Y, X = ctx.shape
-        vol = conv3d_ops.PaddedVolume.from_storage
-        y, a, da = vol(ys, ctx.shape), vol(as_, ctx.shape), vol(dout.contiguous(), ctx.shape)
-        n = B * Z * Y * X
-        s = conv3d_ops.bn_bwd_sums(da, a, y, mu, r)
-        dy = conv3d_ops.bn_bwd_apply(da, a, y, *conv3d_ops.bn_bwd_coefficients(s, n, g, mu, r))
-        return (dy.storage, s[1].to(g.dtype), s[0].to(g.dtype),
-                torch.zeros_like(bias) if ctx.needs_input_grad[3] else None, None, None)
 
 
 class BeforeFusionLayer(nn.Module):

@@ -459,6 +459,21 @@ class VeonOccupancyPath(nn.Module):
         return loss(voxel_semantics, mask_camera, results, img_inputs,
                     prev_img_inputs=prev_img_inputs)
 
+    def forward_features(self, images, img_metas, prev_volumes=None, depth=None):
+        """The training entry: both encoder branches and the decoder, WITHOUT the inference
+        tail (class logits, upsamplings, softmaxes, arg-max) that ``occ_loss`` never reads.
+        Arguments as ``forward``.  -> {'feat_low' (B, C, z, y, x), 'bin_low' (B, 2, z, y, x)}:
+        the decoder's outputs as torch tensors, which ``occ_loss`` accepts.  With the
+        ``hip_train`` switches of the decoder's blocks and heads set, a training-mode
+        forward with grad enabled runs them natively."""
+        B, N = images.shape[:2]
+        hf, wf = self.input_size[0] // 16, self.input_size[1] // 16
+        sem_embed_ds = images.new_zeros((B * N, 1, hf, wf))   # shape carrier only
+        metas = list(img_metas[:5]) + [img_metas[5][None]]
+        feats, supp, depth = self._branches(images, depth)
+        out = self.occ_decoder(sem_embed_ds, feats, [supp], depth, metas, prev_volumes)
+        return {'feat_low': out['feat_occ'], 'bin_low': out['bin_occ']}
+
     def forward(self, images, img_metas, prev_volumes=None, depth=None, with_2d=False,
                 return_features=False):
         """images (B, N, 3, H, W); img_metas = (sensor2egos, ego2globals, intrins,
