@@ -1118,6 +1118,80 @@ int veon_occ_align_bwd(const float *feat, const int64_t *feat_strides, int C, in
                        const int *order, const int *seg_start, int M, const int *occ_rows,
                        float *rows, float *grad, void *stream);
 
+/* ======== occ_align_select.hip ====================================================== */
+
+/* The discrete half of the 2D->3D feature-alignment loss (Proj2Dto3DLoss,
+ * models/semantic_net/loss/occ_loss_utils/occ3d_nuscenes.py:372-508) for ONE sample: which
+ * (camera, voxel) pairs the loss trains on, with which label and weight.  Pairs are
+ * numbered camera-major, p = cam * Xo*Yo*Zo + vox, vox = (x * Yo + y) * Zo + z, the linear
+ * order of the label tensor; n_cam <= 32, n_cam * Xo*Yo*Zo <= 2^31 - 257, n_cls <= 32.
+ * No float atomics and no atomic tickets: every order comes from a scan, repeated calls are
+ * bit-identical.  Nothing is read back; the caller reads head[0] after _mark (it sizes the
+ * entry arrays) and `result` after _emit.
+ *
+ * labels: (Xo,Yo,Zo) uint8, or int64 when labels_are_int64 (values outside [0, 255] count
+ * as "not a class"); a pair is a candidate when 0 <= label < n_cls.  cams: n_cam * 24
+ * floats = rows 0-2 of ego2img (3 x 4, row-major), post_rots (3 x 3), post_trans (3).
+ * grid: 10 HOST floats = step and offset (lower bound + step / 2) of x, y, z, then image
+ * width - 1, height - 1, depth lower and upper bound.  For a candidate, in fp32,
+ *   centre = index * step + offset;  p = ego2img centre;  (a, b) = (p.x, p.y) / p.z;
+ *   (u, v, d) = post_rots (a, b, p.z) + post_trans;
+ *   kept = 0 <= u <= width - 1 && 0 <= v <= height - 1 && depth_lo <= d < depth_hi.
+ *
+ * veon_align_select_groups: the number G of 256-pair workgroups (-1: unsupported size).
+ * veon_align_select_mark writes masks (4 G 64-bit words: the kept bit of every pair),
+ * offsets (G ints: kept pairs in front of each workgroup), head[0] = kept pairs, and clears
+ * head[1 .. n_head); n_head >= 4 + 2 n_cam n_cls + n_cam.
+ *
+ * veon_align_select_classify (n_kept = head[0] >= 1, masks / offsets / head as _mark left
+ * them) fills, for kept entry i in pair order: pair[i], voxels[3i..] = (x, y, z),
+ * classes[4i..] = {label, plain, merged, restricted}, flags[i] (bit 0 det, bit 1 soft).
+ * sem (n_cam,K2,hs,ws) fp32 contiguous is sampled as F.grid_sample(bilinear,
+ * align_corners=False, zeros) does at (u / half_w - 1, v / half_h - 1), half_w =
+ * (width - 1) / 2: ix = ((x + 1) ws - 1) / 2, corners outside the map contribute 0.
+ * gid (K2 ints): merged class of every 2-D class, non-decreasing from 0 in steps of 1.
+ * plain = arg-max of the sampled logits, merged = arg-max over the merged classes of the
+ * per-class maximum, restricted = arg-max within the merged class `label`, first maximum on
+ * ties (logits are taken to be finite: a NaN never wins here, while torch's arg-max
+ * returns it).  soft = merged == label || label >= open_from; det = !soft; with is_last, entry 0 of
+ * the last camera (if it has one) is set in both.
+ *
+ * veon_align_select_emit.  With score (K2,n_kept) (veon_occ_retrieve's cosines at `voxels`
+ * against the K2 class rows) and table_norms (K2) given, the stage-2 rule first clears the
+ * soft bit of entry i when score[k*] >= thr and priority[pred] > priority[merged_i], k* =
+ * arg-max_k score[k] * table_norms[k] and pred the merged arg-max of the same products;
+ * result counts such entries per camera as ignored.  score NULL: no stage 2.  Then, per
+ * term (det by label, soft by merged class), with count = entries of the class in the
+ * camera, norm = sum of priority over the classes present in the camera, per_cam and total
+ * the entries of the camera and of all cameras:
+ *   weight = 1 / count [* priority[class], soft only] / norm * (per_cam / max(total, 1))
+ *            [* det_scale, det only] / batch_size
+ * out_voxels (3 ints), out_labels (restricted for det, plain for soft) and out_weights hold
+ * the det entries first, then the soft entries, each in kept order; `capacity` entries
+ * (n_kept + 1 suffices: only the forced entry is in both).  result (2 + 3 n_cam ints):
+ * n_det, n_soft, det per camera, soft per camera, ignored per camera.  Workspaces: totals
+ * (2 * ceil(n_kept / 256) ints), norms (4 n_cam floats), head as _mark left it. */
+int64_t veon_align_select_groups(int n_cam, int Xo, int Yo, int Zo);
+int veon_align_select_mark(const void *labels, int labels_are_int64, int n_cls,
+                           const float *cams, int n_cam, int Xo, int Yo, int Zo,
+                           const float *grid, unsigned long long *masks, int *offsets,
+                           int *head, int n_head, void *stream);
+int veon_align_select_classify(const void *labels, int labels_are_int64, int n_cls,
+                               const float *cams, int n_cam, int Xo, int Yo, int Zo,
+                               const float *grid, const unsigned long long *masks,
+                               const int *offsets, int *head, const float *sem, int K2,
+                               int hs, int ws, float half_w, float half_h, const int *gid,
+                               int open_from, int n_kept, int is_last, int *pair,
+                               int *voxels, int *classes, int *flags, void *stream);
+int veon_align_select_emit(const int *pair, const int *voxels, const int *classes,
+                           int *flags, int n_kept, int n_cam, int n_vox, int n_cls,
+                           const float *score, const float *table_norms, int K2,
+                           const int *gid, float thr, const float *priority,
+                           float det_scale, int batch_size, int *head, int n_head,
+                           int *totals, float *norms, int *result, int capacity,
+                           int *out_voxels, int *out_labels, float *out_weights,
+                           void *stream);
+
 /* ======== depth_loss.hip ============================================================ */
 
 /* Depth pre-training loss, VeonDepthPretrain.forward_train

@@ -1,0 +1,278 @@
+"""The discrete half of VEON's 2D->3D feature-alignment loss for one sample: which
+(camera, voxel) pairs ``Proj2Dto3DLoss`` trains on, with which label and weight
+(models/semantic_net/loss/occ_loss_utils/occ3d_nuscenes.py:372-508).
+
+The torch formulation (``Proj2Dto3DLoss.select`` of veon_amd/models/semantic_net/
+occ_loss.py, the mirror) projects every voxel centre into every camera and then runs
+``nonzero``, ``searchsorted().tolist()``, one ``grid_sample`` per camera, boolean-mask
+gathers and two ``bincount``s: several dozen launches, about ten of which make the host
+wait for the device.  On a ROCm device ``select_entries`` is native
+(csrc/occ_align_select.hip): mark, scan, compact, classify, [``retrieve_points`` for the
+stage-2 rule,] count, scan, emit, with two read-backs of one small tensor each (the kept
+count, which sizes the lists, and the final counts).  Every order comes from a scan and no
+float is added atomically: repeated calls are bit-identical.  On CPU, or for inputs the
+kernels do not take, it calls the mirror."""
+import ctypes
+
+import torch
+
+from . import _lib
+from .retrieval import retrieve_points
+
+N_CLS = 17                     # merged classes without the free class (class_num - 1)
+_GRID_KEYS = ('x', 'y', 'z', 'depth')
+
+# (device, n_cam, Zo, Yo, Xo) -> dict of workspaces, consumed inside one call.  As with the
+# other native caches, one set per shape and device serves every stream: two streams that
+# select at the same shape concurrently must be ordered by the caller.
+_WORKSPACES = {}
+# (device, kind, values) -> small constant tensors (group ids, priorities): uploaded once,
+# so a call copies nothing from the host
+_CONSTANTS = {}
+
+
+def group_ids(class_reflection):
+    """Merged class of every 2-D class: consecutive equal values of ``class_reflection``
+    form one merged class, numbered in order of appearance -> (list, count)."""
+    ref = [int(v) for v in class_reflection]
+    gid, cur = [], -1
+    for i, v in enumerate(ref):
+        if i == 0 or v != ref[i - 1]:
+            cur += 1
+        gid.append(cur)
+    return gid, cur + 1
+
+
+def _check_args(sem_seg, img_inputs, labels, class_reflection, priority, grid_config, occ_size,
+                ov_class_number, batch, is_last_sample, feat_low, table, high_conf_thr,
+                class_num):
+    if class_num != N_CLS + 1:
+        raise ValueError('class_num must be %d' % (N_CLS + 1))
+    if not isinstance(sem_seg, torch.Tensor) or sem_seg.dim() != 4 or \
+            not sem_seg.is_floating_point() or 0 in sem_seg.shape:
+        raise ValueError('sem_seg must be the (n_cam, K2, h, w) logits of one sample')
+    n_cam, K2 = sem_seg.shape[:2]
+    if len(occ_size) != 3 or min(int(v) for v in occ_size) < 1:
+        raise ValueError('occ_size must be (Z, Y, X)')
+    Zo, Yo, Xo = (int(v) for v in occ_size)
+    if not isinstance(labels, torch.Tensor) or labels.is_floating_point() or \
+            labels.dtype == torch.bool or tuple(labels.shape) != (Xo, Yo, Zo):
+        raise ValueError('labels must be the integer (X, Y, Z) = %s labels of one sample'
+                         % ((Xo, Yo, Zo),))
+    if not isinstance(img_inputs, (list, tuple)) or len(img_inputs) < 11:
+        raise ValueError('img_inputs must hold the 11 tensors of the reference')
+    if img_inputs[0].dim() < 2:
+        raise ValueError('img_inputs[0] must end in the image size (H, W)')
+    B = img_inputs[3].shape[0]
+    for i, tail in ((3, (3, 3)), (4, (3, 3)), (5, (3,)), (8, (4, 4)), (9, (4, 4)), (10, (4, 4))):
+        if tuple(img_inputs[i].shape) != (B, n_cam) + tail:
+            raise ValueError('img_inputs[%d] must be %s, got %s'
+                             % (i, (B, n_cam) + tail, tuple(img_inputs[i].shape)))
+    if not 0 <= batch < B:
+        raise ValueError('batch %d outside [0, %d)' % (batch, B))
+    if is_last_sample != (batch == B - 1):
+        raise ValueError('is_last_sample contradicts batch %d of %d' % (batch, B))
+    gid, n_groups = group_ids(class_reflection)
+    if len(gid) != K2 or n_groups != N_CLS:
+        raise ValueError('class_reflection must merge the %d 2-D classes into %d'
+                         % (K2, N_CLS))
+    if len(priority) != N_CLS:
+        raise ValueError('priority must hold one value per merged class (%d)' % N_CLS)
+    if not 0 <= ov_class_number <= N_CLS:
+        raise ValueError('ov_class_number outside [0, %d]' % N_CLS)
+    if grid_config is None or any(k not in grid_config or len(grid_config[k]) != 3
+                                  for k in _GRID_KEYS):
+        raise ValueError('grid_config must give [lower, upper, step] for x, y, z and depth')
+    for t in (labels, img_inputs[3], img_inputs[4], img_inputs[5], img_inputs[8],
+              img_inputs[9], img_inputs[10]):
+        if t.device != sem_seg.device:
+            raise ValueError('tensors on different devices: %s vs %s' % (t.device,
+                                                                         sem_seg.device))
+    stage2 = [feat_low is not None, table is not None, high_conf_thr is not None]
+    if any(stage2) != all(stage2):
+        raise ValueError('the stage-2 rule needs feat_low, table and high_conf_thr together')
+    if all(stage2):
+        if not isinstance(feat_low, torch.Tensor) or feat_low.dim() != 5 or \
+                feat_low.shape[0] != B:
+            raise ValueError('feat_low must be the (B, C, z, y, x) volume of the batch')
+        if table.dim() != 2 or tuple(table.shape) != (K2 + 1, feat_low.shape[1]):
+            raise ValueError('table must be (K2 + 1, C) = %s' % ((K2 + 1, feat_low.shape[1]),))
+        if feat_low.device != sem_seg.device or table.device != sem_seg.device:
+            raise ValueError('feat_low and table must be on %s' % sem_seg.device)
+
+
+def _mirror(sem_seg, img_inputs, labels, class_reflection, priority, grid_config, occ_size,
+            ov_class_number, batch, feat_low, table, high_conf_thr):
+    """The torch mirror on sample ``batch``: the sample's tensors stand in for the whole
+    batch as expanded views (nothing is copied, only sample ``batch`` is evaluated)."""
+    from .models.semantic_net.occ_loss import Proj2Dto3DLoss
+    B = img_inputs[3].shape[0]
+    stage2 = feat_low is not None
+    mod = Proj2Dto3DLoss(grid_config=grid_config, ov_class_number=ov_class_number,
+                         high_conf_thr=high_conf_thr if stage2 else 0.99,
+                         stage2_start=0 if stage2 else 1,
+                         priority=torch.as_tensor(priority).detach().cpu())
+    if not stage2:
+        feat_low = sem_seg.new_zeros((B, 1, 1, 1, 1))
+        table = sem_seg.new_zeros((sem_seg.shape[1] + 1, 1))
+    return mod._select_torch(
+        feat_low, sem_seg[None].expand((B,) + tuple(sem_seg.shape)), img_inputs,
+        labels[None].expand((B,) + tuple(labels.shape)), class_reflection, table, occ_size,
+        only=batch)[0]
+
+
+def _constant(device, kind, values, dtype):
+    key = (str(device), kind, tuple(values))
+    t = _CONSTANTS.get(key)
+    if t is None:
+        t = _CONSTANTS[key] = torch.tensor(list(values), dtype=dtype).to(device)
+    return t
+
+
+def _workspace(device, n_cam, occ_size):
+    key = (str(device), n_cam) + tuple(occ_size)
+    ws = _WORKSPACES.get(key)
+    if ws is None:
+        Zo, Yo, Xo = occ_size
+        groups = int(_lib.lib().veon_align_select_groups(n_cam, Xo, Yo, Zo))
+        if groups < 0:
+            raise ValueError('select_entries: unsupported size, %d cameras on a %s grid'
+                             % (n_cam, tuple(occ_size)))
+        n_head = 4 + 2 * n_cam * N_CLS + n_cam
+        ws = _WORKSPACES[key] = dict(
+            masks=torch.empty(4 * groups, dtype=torch.int64, device=device),
+            offsets=torch.empty(groups, dtype=torch.int32, device=device),
+            head=torch.empty(n_head, dtype=torch.int32, device=device),
+            norms=torch.empty(4 * n_cam, dtype=torch.float32, device=device),
+            result=torch.empty(2 + 3 * n_cam, dtype=torch.int32, device=device))
+    return ws
+
+
+def _entry_workspace(ws, n, device):
+    """Per-entry arrays of the workspace set, grown in steps of 65 536 entries."""
+    if ws.get('capacity', 0) < n:
+        cap = -(-n // 65536) * 65536
+        ws.update(capacity=cap,
+                  pair=torch.empty(cap, dtype=torch.int32, device=device),
+                  voxels=torch.empty((cap, 3), dtype=torch.int32, device=device),
+                  classes=torch.empty((cap, 4), dtype=torch.int32, device=device),
+                  flags=torch.empty(cap, dtype=torch.int32, device=device),
+                  totals=torch.empty(2 * (cap // 256), dtype=torch.int32, device=device))
+    return ws
+
+
+def _native(sem_seg, img_inputs, labels, class_reflection, priority, grid_config, occ_size,
+            ov_class_number, batch, is_last_sample, feat_low, table, high_conf_thr):
+    dev = _lib.require_device(sem_seg, labels)
+    f32 = torch.float32
+    n_cam, K2, hs, ws_ = sem_seg.shape
+    Zo, Yo, Xo = occ_size
+    B = img_inputs[3].shape[0]
+    height, width = (int(v) for v in img_inputs[0].shape[-2:])
+    if height < 2 or width < 2:
+        raise ValueError('the image must be at least 2 x 2')
+    sem = sem_seg.detach().contiguous()
+    if labels.dtype not in (torch.uint8, torch.int64):
+        labels = labels.long()
+    labels = labels.contiguous()
+    is64 = int(labels.dtype == torch.int64)
+
+    # the mirror's 4 x 4 algebra on this sample's cameras; inv_ex reads no error flag back
+    intrins, post_rots, post_trans = (img_inputs[i][batch].to(f32) for i in (3, 4, 5))
+    lidarego2global, cam2camego, camego2global = (img_inputs[i][batch].to(f32)
+                                                  for i in (8, 9, 10))
+    cam2img = torch.eye(4, dtype=f32, device=dev).repeat(n_cam, 1, 1)
+    cam2img[:, :3, :3] = intrins
+    ego2img = cam2img @ (torch.linalg.inv_ex(camego2global @ cam2camego).inverse
+                         @ lidarego2global)
+    cams = torch.cat([ego2img[:, :3].reshape(n_cam, 12), post_rots.reshape(n_cam, 9),
+                      post_trans.reshape(n_cam, 3)], 1).contiguous()
+    gc = grid_config
+    grid = (ctypes.c_float * 10)(
+        gc['x'][2], gc['x'][0] + gc['x'][2] / 2, gc['y'][2], gc['y'][0] + gc['y'][2] / 2,
+        gc['z'][2], gc['z'][0] + gc['z'][2] / 2, width - 1, height - 1,
+        gc['depth'][0], gc['depth'][1])
+    grid_p = ctypes.cast(grid, ctypes.c_void_p)
+
+    gid_list, _ = group_ids(class_reflection)
+    gid = _constant(dev, 'gid', gid_list, torch.int32)
+    if isinstance(priority, torch.Tensor) and priority.device == dev:
+        prio = priority.detach().to(f32).contiguous()
+    else:
+        prio = _constant(dev, 'priority', [float(v) for v in priority], f32)
+
+    ws = _workspace(dev, n_cam, occ_size)
+    n_head = ws['head'].shape[0]
+    _lib.launch('veon_align_select_mark', dev, labels, is64, N_CLS, cams, n_cam, Xo, Yo, Zo,
+                grid_p, ws['masks'], ws['offsets'], ws['head'], n_head)
+    n_kept = int(ws['head'][:1].cpu()[0])                 # read-back 1: sizes the lists
+    zeros = torch.zeros(n_cam, dtype=torch.int64, device=dev)
+    if n_kept == 0:
+        return dict(voxels=torch.empty((0, 3), dtype=torch.int32, device=dev),
+                    labels=torch.empty((0,), dtype=torch.int32, device=dev),
+                    weights=torch.empty((0,), dtype=f32, device=dev), n_det=0, det=zeros,
+                    soft=zeros.clone(), ignored=zeros.clone())
+    _entry_workspace(ws, n_kept, dev)
+    _lib.launch('veon_align_select_classify', dev, labels, is64, N_CLS, cams, n_cam, Xo, Yo,
+                Zo, grid_p, ws['masks'], ws['offsets'], ws['head'], sem, K2, hs, ws_,
+                (width - 1) / 2, (height - 1) / 2, gid, N_CLS - ov_class_number, n_kept,
+                int(is_last_sample), ws['pair'], ws['voxels'], ws['classes'], ws['flags'])
+    score = tnorm = None
+    thr = 0.0
+    if feat_low is not None:
+        rows = table.detach().to(f32)[:-1].contiguous()
+        score, _ = retrieve_points(feat_low.detach(), None, ws['voxels'][:n_kept], rows,
+                                   occ_size, batch)
+        tnorm = rows.norm(dim=1)
+        thr = float(high_conf_thr)
+    cap = n_kept + 1                                      # the forced entry is in both terms
+    voxels = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+    out_labels = torch.empty((cap,), dtype=torch.int32, device=dev)
+    weights = torch.empty((cap,), dtype=f32, device=dev)
+    _lib.launch('veon_align_select_emit', dev, ws['pair'], ws['voxels'], ws['classes'],
+                ws['flags'], n_kept, n_cam, Xo * Yo * Zo, N_CLS, score, tnorm, K2, gid, thr,
+                prio, 0.0 if ov_class_number == N_CLS else 1.0, B, ws['head'], n_head,
+                ws['totals'], ws['norms'], ws['result'], cap, voxels, out_labels, weights)
+    counts = ws['result'].long()                          # a copy: the workspace is reused
+    host = counts.cpu()                                   # read-back 2: the final counts
+    n_det, n_soft = int(host[0]), int(host[1])
+    n = n_det + n_soft
+    return dict(voxels=voxels[:n], labels=out_labels[:n], weights=weights[:n], n_det=n_det,
+                det=counts[2:2 + n_cam], soft=counts[2 + n_cam:2 + 2 * n_cam],
+                ignored=counts[2 + 2 * n_cam:])
+
+
+def select_entries(sem_seg, img_inputs, labels, class_reflection, priority, grid_config,
+                   occ_size, ov_class_number, batch=0, is_last_sample=None, feat_low=None,
+                   table=None, high_conf_thr=None, class_num=18):
+    """The entries of sample ``batch`` the alignment loss trains on: what
+    ``Proj2Dto3DLoss.select`` puts in its list for that sample.
+
+    sem_seg: ``sem_seg_2d[batch]``, the (n_cam, K2, h, w) class logits of the sample (any
+    map size).  img_inputs: the reference's 11 tensors for the whole batch; the image size
+    is ``img_inputs[0].shape[-2:]``.  labels: the sample's masked labels (X, Y, Z), any
+    integer dtype (uint8 and int64 are read in place).  class_reflection: K2 values whose
+    runs merge the 2-D classes into 17; priority: 17 values; grid_config: [lower, upper,
+    step] for 'x', 'y', 'z', 'depth'; occ_size = (Z, Y, X).  is_last_sample (default:
+    ``batch`` is the last of the batch) must agree with ``batch``: the last sample gets the
+    reference's forced entry.  The stage-2 rule applies when ``feat_low`` (B, C, z, y, x),
+    ``table`` (K2 + 1, C) and ``high_conf_thr`` are all given.
+
+    -> dict: ``voxels`` (n, 3) int32 (x, y, z), ``labels`` (n,) int32, ``weights`` (n,),
+    ``n_det`` (the first n_det entries are the det term), and per-camera ``det``, ``soft``,
+    ``ignored`` (int64).  Malformed arguments raise ValueError.  Native for fp32 logits (and
+    fp32 ``feat_low``) on a ROCm device; otherwise the torch mirror."""
+    occ_size = tuple(int(v) for v in occ_size) if len(occ_size) == 3 else tuple(occ_size)
+    batch, ov_class_number = int(batch), int(ov_class_number)
+    if is_last_sample is None and isinstance(img_inputs, (list, tuple)) and len(img_inputs) > 3:
+        is_last_sample = batch == img_inputs[3].shape[0] - 1
+    _check_args(sem_seg, img_inputs, labels, class_reflection, priority, grid_config, occ_size,
+                ov_class_number, batch, bool(is_last_sample), feat_low, table, high_conf_thr,
+                class_num)
+    args = (sem_seg, img_inputs, labels, class_reflection, priority, grid_config, occ_size,
+            ov_class_number, batch)
+    native = sem_seg.is_cuda and sem_seg.dtype == torch.float32 and \
+        (feat_low is None or feat_low.dtype == torch.float32)
+    if not native:
+        return _mirror(*args, feat_low, table, high_conf_thr)
+    return _native(*args, bool(is_last_sample), feat_low, table, high_conf_thr)

@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ...align_loss import voxel_cosine
+from ...align_select import select_entries
 from ...occ_bin_loss import bin_occ_loss
 from ...retrieval import retrieve_points
 
@@ -70,7 +71,14 @@ def _balanced_weights(cam, cls, n_cam, n_cls, priority, scaled):
 class Proj2Dto3DLoss(nn.Module):
     """The 2D->3D feature-alignment loss from the low-resolution feature volume.
     ``epoch`` is set by the training loop; the stage-2 rule applies from
-    ``stage2_start`` on.  ``priority``: one value per merged class."""
+    ``stage2_start`` on.  ``priority``: one value per merged class.
+
+    ``hip_select`` (class attribute, default False): opt-in native selection.  When set,
+    ``select`` takes every sample's entries from ``align_select.select_entries``
+    (csrc/occ_align_select.hip on a ROCm device with fp32 inputs: two small read-backs per
+    sample in place of the torch sequence's 26 synchronising calls; the torch sequence
+    below for anything else)."""
+    hip_select = False
 
     def __init__(self, grid_config=None, loss_det_weight=1.0, loss_soft_weight=1.0,
                  ov_class_number=0, high_conf_thr=0.99, stage2_start=2, priority=None):
@@ -107,7 +115,29 @@ class Proj2Dto3DLoss(nn.Module):
     @torch.no_grad()
     def select(self, feat_low, sem_seg_2d, img_inputs, voxel_semantics, class_reflection,
                ov_classifier_weight, occ_size, class_num=18):
-        """-> one dict per sample: ``voxels`` (n, 3) int32 (x, y, z), ``labels`` (n,)
+        """The entry lists of ``_select_torch``; with ``hip_select``, sample by sample from
+        ``select_entries``."""
+        if not self.hip_select:
+            return self._select_torch(feat_low, sem_seg_2d, img_inputs, voxel_semantics,
+                                      class_reflection, ov_classifier_weight, occ_size,
+                                      class_num)
+        stage2 = {}
+        if self.epoch >= self.stage2_start:
+            stage2 = dict(feat_low=feat_low.detach(), table=ov_classifier_weight.detach(),
+                          high_conf_thr=self.high_conf_thr)
+        B = sem_seg_2d.shape[0]
+        return [select_entries(sem_seg_2d[b].to(feat_low.dtype), img_inputs,
+                               voxel_semantics[b], class_reflection, self.priority,
+                               self.grid_config, occ_size, self.ov_class_number, batch=b,
+                               is_last_sample=b == B - 1, class_num=class_num, **stage2)
+                for b in range(B)]
+
+    @torch.no_grad()
+    def _select_torch(self, feat_low, sem_seg_2d, img_inputs, voxel_semantics,
+                      class_reflection, ov_classifier_weight, occ_size, class_num=18,
+                      only=None):
+        """``only``: evaluate that sample alone (a one-element list).
+        -> one dict per sample: ``voxels`` (n, 3) int32 (x, y, z), ``labels`` (n,)
         int32 rows of the table, ``weights`` (n,), ``n_det`` (the first n_det entries
         are the det term, the rest the soft term), and the per-camera counts ``det``,
         ``soft`` and ``ignored`` (soft entries dropped by the stage-2 rule).  The
@@ -129,7 +159,7 @@ class Proj2Dto3DLoss(nn.Module):
             (depth < self.grid_config['depth'][1]) & (depth >= self.grid_config['depth'][0])
         det_scale = 0.0 if class_num == self.ov_class_number else 1.0
         out = []
-        for b in range(B):
+        for b in (range(B) if only is None else [only]):
             gt_all = voxel_semantics[b].reshape(-1).long()
             kept = in_view[b] & ((gt_all < class_num) & (gt_all >= 0))[None]
             cam, vox = kept.nonzero(as_tuple=True)          # camera-major, voxel order
@@ -241,12 +271,15 @@ class OccLossFB(nn.Module):
     ``hip_train`` (keyword and attribute, default False): opt-in native occupancy term.
     When set and ``bin_occ`` is an fp32 tensor on a ROCm device, ``loss_voxel`` takes it
     from ``occ_bin_loss.bin_occ_loss`` (csrc/occ_bin_loss.hip: upsampling and cross entropy
-    fused in both directions, nothing read back); anything else runs the torch sequence."""
+    fused in both directions, nothing read back); anything else runs the torch sequence.
+
+    ``hip_select`` (keyword and attribute, default False): opt-in native entry selection of
+    the alignment loss, passed down to ``Proj2Dto3DLoss.hip_select``."""
 
     def __init__(self, out_channel=18, loss_weight_cfg=None, empty_idx=17, ignore_idx=255,
                  balance_cls_weight=True, grid_config=None, mode='nuscenes',
                  high_conf_thr=0.985, stage2_start=2, priority=None, ov_class_number=17,
-                 class_frequencies=None, hip_train=False):
+                 class_frequencies=None, hip_train=False, hip_select=False):
         super().__init__()
         self.hip_train = bool(hip_train)
         if mode not in ('semkitti', 'nuscenes'):
@@ -259,6 +292,8 @@ class OccLossFB(nn.Module):
         self.proj2dto3dloss = Proj2Dto3DLoss(
             grid_config=grid_config, ov_class_number=ov_class_number, priority=priority,
             high_conf_thr=high_conf_thr, stage2_start=stage2_start)
+        if hip_select:          # otherwise the class attribute of Proj2Dto3DLoss decides
+            self.hip_select = True
         self.bin_occ_loss = BCE_BinOcc_Loss
         self.bin_class_weights = torch.tensor([1.0, 0.5])       # occupied, free
         if balance_cls_weight and class_frequencies is not None:
@@ -274,6 +309,14 @@ class OccLossFB(nn.Module):
     @epoch.setter
     def epoch(self, value):
         self.proj2dto3dloss.epoch = value
+
+    @property
+    def hip_select(self):
+        return self.proj2dto3dloss.hip_select
+
+    @hip_select.setter
+    def hip_select(self, value):
+        self.proj2dto3dloss.hip_select = bool(value)
 
     def _bin_weights_on(self, device):
         """``bin_class_weights`` as fp32 on ``device``, copied once per device and per value
