@@ -1280,6 +1280,77 @@ int veon_occ_bin_loss_fwd(const float *logits, const int64_t *logit_strides, int
 int veon_occ_bin_loss_bwd(const float *coef, const float *out, const float *gout, int B,
                           int zi, int yi, int xi, float *grad, void *stream);
 
+/* ======== fusion_train.hip ========================================================== */
+
+/*
+ * ---- training of the lift's 2-D fusion (CatFusionLift, semantic_net/layers.py:154-199)
+ * on token rows ----
+ * x (N, Cin, Hin, Win) is an fp32 NCHW map, contiguous; the lift's map is H x W, M = N*H*W
+ * tokens; rc / drc are fp32 rows [M][C] and the map owns their columns coff .. coff + Cin.
+ * The filter is torch's bilinear resize (align_corners = False, no antialias) read from
+ * per-axis tables the host computes in fp32 once per shape pair (taby: Hin -> H, tabx:
+ * Win -> W).  A table of `in` source and `out` destination positions is 3 * out + 2 * in
+ * 32-bit words on the device, 16-byte aligned:
+ *     i0[out] | i1[out] | l1[out] (float) | first[in] | last[in]
+ * src = max((d + 0.5f) * ((float)in / out) - 0.5f, 0) with the multiply-subtract rounded
+ * once (torch's kernels contract it), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0;
+ * source s is read by the destinations first[s] <= d < last[s] (i0 is monotone: one range).  Indices read from a table are clamped to their
+ * axis.  A map already at H x W is copied (weights 1 and 0) and takes no tables (NULL).
+ * Cin % 64 == 0, C % 4 == 0, coff % 4 == 0, every tensor below 2^31 elements and
+ * N * max(H, Hin) <= 65535, otherwise VEON_ERR_BAD_ARG.
+ *
+ * veon_fusion_resize_cat     : rc[:, coff : coff + Cin] = resize(x), channels-last.
+ * veon_fusion_resize_adjoint : dx = resize^T(drc[:, coff : coff + Cin]) in gather form:
+ *                              every source pixel adds the tokens whose footprint holds it
+ *                              in index order; a pixel no token reads is written as ZERO.
+ *                              No atomics, no cleared output, bit-reproducible.
+ */
+int veon_fusion_resize_cat(const float *x, float *rc, const void *taby, const void *tabx,
+                           int N, int Cin, int Hin, int Win, int H, int W, int C, int coff,
+                           void *stream);
+int veon_fusion_resize_adjoint(const float *drc, float *dx, const void *taby,
+                               const void *tabx, int N, int Cin, int Hin, int Win, int H,
+                               int W, int C, int coff, void *stream);
+
+/*
+ * Both LayerNorms of the module from one read of a row: xn1 half [M][C1 + C2] =
+ * LN1(rc), xn2 half [M][C2] = LN2(rc[:, C1:]); biased variance, eps inside the sqrt,
+ * two-pass statistics from registers, one wave per row.
+ * C1 % 64 == 0, C2 % 64 == 0, C1 + C2 <= 2048, M * (C1 + C2) < 2^31.
+ */
+int veon_fusion_dual_ln(const float *rc, const float *gamma1, const float *beta1,
+                        const float *gamma2, const float *beta2, void *xn1, void *xn2, int M,
+                        int C1, int C2, float eps1, float eps2, void *stream);
+
+/*
+ * Their backward at the stored fp32 rows rc (statistics recomputed): dxn1 half
+ * [M][C1 + C2], dxn2 half [M][C2] -> drc fp32 [M][C1 + C2], whose columns from C1 on are
+ * the sum of both branches, and sums fp32 [2 (C1 + C2) + 2 C2] =
+ * dgamma1 | dbeta1 | dgamma2 | dbeta2.  Two stages in a fixed order, no atomics;
+ * `workspace`: veon_fusion_dual_ln_bwd_workspace_bytes(C1, C2) bytes (host-only; -1:
+ * unsupported widths).  Widths as veon_fusion_dual_ln.  drc must not alias rc.
+ */
+int64_t veon_fusion_dual_ln_bwd_workspace_bytes(int C1, int C2);
+int veon_fusion_dual_ln_bwd(const void *dxn1, const void *dxn2, const float *rc,
+                            const float *gamma1, const float *gamma2, float *drc,
+                            float *sums, void *workspace, int64_t workspace_bytes, int M,
+                            int C1, int C2, float eps1, float eps2, void *stream);
+
+/*
+ * Around the ReLU.  y1 half [M][ld1], y2 half [M][ld2] are the GEMM outputs (bias and
+ * ReLU applied by the GEMM's epilogue), of which the first p1 / p2 columns count.
+ * veon_fusion_join       : out fp32 [M][p1 + p2] = cat(y1[:, :p1], y2[:, :p2]).
+ * veon_fusion_relu_split : dy1 half [M][ld1], dy2 half [M][ld2] = the columns of dout
+ *                          fp32 [M][p1 + p2] where the stored output is positive, zero
+ *                          elsewhere and in the padding columns.
+ * p1 % 4 == 0, p2 % 4 == 0, ld % 8 == 0, ld >= p, M * (ld1 + ld2) < 2^31.
+ */
+int veon_fusion_join(const void *y1, const void *y2, float *out, int M, int p1, int p2,
+                     int ld1, int ld2, void *stream);
+int veon_fusion_relu_split(const float *dout, const void *y1, const void *y2, void *dy1,
+                           void *dy2, int M, int p1, int p2, int ld1, int ld2,
+                           void *stream);
+
 /* ======== volume_handover.hip ======================================================= */
 
 /* Hand-over between the padded half rows the prediction heads train on and the fp32

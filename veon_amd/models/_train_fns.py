@@ -11,7 +11,7 @@ between two kernels is rounded to fp16: loss scaling is the caller's business.
 import torch
 import torch.nn.functional as F
 
-from .. import conv3d_ops, vit_ops
+from .. import conv3d_ops, fusion_ops, vit_ops
 
 LORA_PAD = 64   # the rank is zero-padded to the GEMM's and the weight gradient's tile width
 
@@ -181,6 +181,91 @@ class _LoRALinearTrainFn(torch.autograd.Function):
         if need[4]:
             dlb = (vit_ops.linear_wgrad(dy, u)[:, :r] * s).to(lora_b.dtype)
         return da, dw, db, dla, dlb, None
+
+
+def _pad_rows64(t):
+    """fp32 [p, ...] -> fp32 [pad64(p), ...], rows p.. zero (the GEMM's and the weight
+    gradient's tile width, as the LoRA rank)."""
+    t = t.detach().float()
+    pad = -t.shape[0] % LORA_PAD
+    return F.pad(t, (0, 0) * (t.dim() - 1) + (0, pad)) if pad else t.contiguous()
+
+
+class _CatFusionTrainFn(torch.autograd.Function):
+    """``CatFusionLift`` for training (csrc/fusion_train.hip): fp32 NCHW maps x1, x2 ->
+    relu(cat(conv1(LN1(cat(r(x1), r(x2)))), conv2(LN2(r(x2))))), r the bilinear resize to
+    ``size``, as the NCHW view of fp32 channels-last rows.  The two 1x1 convs are GEMMs on
+    half rows whose epilogue adds the bias and applies the ReLU; their output widths are
+    zero-padded to multiples of 64 (weight rows, bias) and the padding rows of dW and db are
+    dropped.
+
+    Saved for backward: the resized fp32 rows ``rc`` and the two half GEMM outputs.  The
+    normalised half rows are NOT saved: they are as large as ``rc`` again (65 MB against
+    78 MB at the VEON shape) and one more ``dual_layernorm`` of ``rc`` in backward, run only
+    when a conv weight asks for its gradient, rebuilds them bit for bit.  Parameter
+    gradients are fp32 in the parameters' own layout, only those ``needs_input_grad`` asks
+    for; an input that needs no gradient gets no adjoint launch."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, g1, b1, w1, c1, g2, b2, w2, c2, size, eps1, eps2):
+        x1c, x2c = x1.detach().contiguous(), x2.detach().contiguous()
+        N, C1 = x1c.shape[:2]
+        p1, p2 = w1.shape[0], w2.shape[0]
+        rc = fusion_ops.resize_cat(x1c, x2c, size)
+        xn1, xn2 = fusion_ops.dual_layernorm(
+            rc, C1, g1.detach().contiguous(), b1.detach().contiguous(), eps1,
+            g2.detach().contiguous(), b2.detach().contiguous(), eps2)
+        y1 = vit_ops.linear(xn1, vit_ops.to_bf16(_pad_rows64(w1.view(p1, -1))),
+                            _pad_rows64(c1), vit_ops.EPI_AFFINE_RELU)
+        y2 = vit_ops.linear(xn2, vit_ops.to_bf16(_pad_rows64(w2.view(p2, -1))),
+                            _pad_rows64(c2), vit_ops.EPI_AFFINE_RELU)
+        ctx.size, ctx.eps = tuple(size), (eps1, eps2)
+        ctx.shapes = (x1.shape, x2.shape)
+        ctx.save_for_backward(rc, y1, y2, g1, b1, w1, g2, b2, w2)
+        out = fusion_ops.join(y1, y2, p1, p2)
+        return out.view(N, size[0], size[1], p1 + p2).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        rc, y1, y2, g1, b1, w1, g2, b2, w2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        p1, p2 = w1.shape[0], w2.shape[0]
+        C = rc.shape[1]
+        C1 = C - w2[0].numel()
+        (eps1, eps2), size = ctx.eps, ctx.size
+        g1, g2 = g1.detach().contiguous(), g2.detach().contiguous()
+        # channels-last rows of the upstream gradient (no copy when it arrives that way)
+        rows = dout.float().permute(0, 2, 3, 1).contiguous().view(-1, p1 + p2)
+        dy1, dy2 = fusion_ops.relu_split(rows, y1, y2, p1, p2)
+        dc1 = vit_ops.colsum(dy1)[:p1].to(w1.dtype) if need[5] else None
+        dc2 = vit_ops.colsum(dy2)[:p2].to(w2.dtype) if need[9] else None
+        dw1 = dw2 = None
+        if need[4] or need[8]:
+            xn1, xn2 = fusion_ops.dual_layernorm(
+                rc, C1, g1, b1.detach().contiguous(), eps1, g2, b2.detach().contiguous(),
+                eps2)
+            if need[4]:
+                dw1 = vit_ops.linear_wgrad(dy1, xn1)[:p1].view(w1.shape).to(w1.dtype)
+            if need[8]:
+                dw2 = vit_ops.linear_wgrad(dy2, xn2)[:p2].view(w2.shape).to(w2.dtype)
+            del xn1, xn2
+        dx1 = dx2 = dg1 = db1 = dg2 = db2 = None
+        if need[0] or need[1] or need[2] or need[3] or need[6] or need[7]:
+            # data gradients as GEMMs on the transposed padded weights [Cin][pad64(p)]
+            dxn1 = vit_ops.linear(
+                dy1, vit_ops.to_bf16(_pad_rows64(w1.view(p1, -1)).t().contiguous()))
+            dxn2 = vit_ops.linear(
+                dy2, vit_ops.to_bf16(_pad_rows64(w2.view(p2, -1)).t().contiguous()))
+            drc, dg1, db1, dg2, db2 = fusion_ops.dual_layernorm_bwd(
+                dxn1, dxn2, rc, C1, g1, eps1, g2, eps2)
+            if need[0]:
+                dx1 = fusion_ops.resize_adjoint(drc, ctx.shapes[0], size, 0)
+            if need[1]:
+                dx2 = fusion_ops.resize_adjoint(drc, ctx.shapes[1], size, C1)
+        return (dx1, dx2, dg1 if need[2] else None, db1 if need[3] else None, dw1, dc1,
+                dg2 if need[6] else None, db2 if need[7] else None, dw2, dc2, None, None,
+                None)
 
 
 # ------------------------------------------------- padded volumes (storage tensors)

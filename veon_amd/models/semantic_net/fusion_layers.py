@@ -11,8 +11,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ... import vit_ops
+from ... import fusion_ops, vit_ops
 from .._native_cache import NativeCacheMixin
+from .._train_fns import _CatFusionTrainFn
 from ... import half as _half
 
 
@@ -56,7 +57,16 @@ class CatFusionLift(NativeCacheMixin, nn.Module):
 
     """LN + 1x1 conv of cat(x1, x2) -> C/4 channels, LN + 1x1 conv of x2 ->
     3C/4, concatenated, ReLU; both inputs are first resized to the lift's
-    feature-map shape."""
+    feature-map shape.
+
+    ``hip_train`` (class attribute, default False): opt-in native TRAINING path.  When
+    set, a call under autograd on ROCm fp32 maps whose widths the kernels take runs
+    ``_CatFusionTrainFn`` (csrc/fusion_train.hip: resize + cat into channels-last rows, both
+    LayerNorms from one read, MFMA GEMMs with bias + ReLU, and their backwards in HIP) and
+    returns the NCHW view of fp32 channels-last rows, which the lift reads without a
+    copy.  Anything else takes the torch formulation below."""
+
+    hip_train = False
 
     def __init__(self, in_channels_1, in_channels_2, out_channels):
         super().__init__()
@@ -102,6 +112,29 @@ class CatFusionLift(NativeCacheMixin, nn.Module):
         out = torch.cat([y1, y2], dim=1).view(N, H, W, -1)       # NHWC bf16
         return out.permute(0, 3, 1, 2)                            # NCHW view of it
 
+    def _hip_train_ok(self, x1, x2):
+        """The native training path's own test: the switch, autograd, ROCm fp32 maps and
+        parameters, both input widths multiples of 64 and their sum at most 2048 (the dual
+        LayerNorm's row), both output widths multiples of 4 (the GEMM's)."""
+        if not (self.hip_train and torch.is_grad_enabled() and torch.is_tensor(x1)
+                and torch.is_tensor(x2) and x1.is_cuda and x2.is_cuda
+                and x1.dtype == x2.dtype == torch.float32 and x1.dim() == x2.dim() == 4):
+            return False
+        c1, c2 = self.input_proj_1[1], self.input_proj_2[1]
+        C1, C2 = c1.in_channels - c2.in_channels, c2.in_channels
+        return (x1.shape[1] == C1 and x2.shape[1] == C2 and C1 % 64 == 0 and C2 % 64 == 0
+                and C1 + C2 <= fusion_ops.MAX_C and c1.out_channels % 4 == 0
+                and c2.out_channels % 4 == 0 and c1.bias is not None
+                and c2.bias is not None
+                and all(p.dtype == torch.float32 and p.is_cuda for p in self.parameters()))
+
+    def _hip_train_forward(self, x1, x2, size):
+        (ln1, c1), (ln2, c2) = self.input_proj_1, self.input_proj_2
+        return _CatFusionTrainFn.apply(x1, x2, ln1.weight, ln1.bias, c1.weight, c1.bias,
+                                       ln2.weight, ln2.bias, c2.weight, c2.bias,
+                                       tuple(int(v) for v in size),
+                                       ln1.eps, ln2.eps)
+
     @staticmethod
     def _resize(x, size):
         # same op as the reference's F.interpolate(x.contiguous(), ...); on a GPU
@@ -116,6 +149,8 @@ class CatFusionLift(NativeCacheMixin, nn.Module):
 
     def forward(self, x1, x2, spatial_shape: Tuple[int, int]):
         spatial_shape = tuple(spatial_shape)
+        if self._hip_train_ok(x1, x2):
+            return self._hip_train_forward(x1, x2, spatial_shape)
         if tuple(x2.shape[-2:]) != spatial_shape:
             x2 = self._resize(x2, spatial_shape)
         if tuple(x1.shape[-2:]) != spatial_shape:
