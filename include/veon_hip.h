@@ -962,6 +962,15 @@ int veon_gelu_bf16(const void *y, void *h, int64_t n, void *stream);
 int veon_gelu_bwd_bf16(const void *dh, const void *y, void *dy, int64_t n, void *stream);
 
 /*
+ * The same pair for CLIP's QuickGELU: h = y * sigma(1.702 y) and
+ * dy = dh * (sigma + 1.702 * y * sigma * (1 - sigma)), sigma = sigmoid(1.702 y), in fp32
+ * from the stored half pre-activation.  n % 8 == 0; outputs must not alias inputs.
+ */
+int veon_quickgelu_bf16(const void *y, void *h, int64_t n, void *stream);
+int veon_quickgelu_bwd_bf16(const void *dh, const void *y, void *dy, int64_t n,
+                            void *stream);
+
+/*
  * Backward of nn.LayerNorm over the last axis at its stored fp32 input x [T][d]; the row
  * statistics are recomputed.  `dout`: fp32 [T][d] (dout_half == 0) or half [T][d].
  * dx fp32 [T][d]; sums[2][d] (fp32): [0] dgamma = sum dout * xhat, [1] dbeta = sum dout.
@@ -1001,6 +1010,51 @@ int veon_vit_attention_bwd(const void *qkv, const void *out, const void *dout,
                            const float *lse, void *dqkv, void *workspace,
                            int64_t workspace_bytes, int B, int T, int H, int head_dim,
                            float scale, void *stream);
+
+/*
+ * The same pair with a dense additive bias (the CLIP tail under autograd).  qkv, out, lse,
+ * scale and the workspace are exactly those of the unbiased pair: raw q, lse in log2 units
+ * in rows of veon_vit_attention_stats_len(T) floats, columns T.. never used.
+ *
+ * `bias`: fp32, natural-log units, added to scale * q.k.  Per (b, h) it is a [Tb][Tb]
+ * matrix, Tb = T - border, rows Tb floats long (no alignment requirement on Tb), at
+ * bias + b * bias_sb + h * bias_sh (element strides >= 0; 0 broadcasts the axis).
+ * `border` is 0 or 1.  With border = 1 the matrix is patch-to-patch: token 0 (the class
+ * token) has bias 0 as a query and as a key, by index, and nothing outside [0, Tb)^2 of a
+ * matrix is read or written.  T = 1 with border = 1 is legal: the bias is never read and
+ * may be NULL.
+ *
+ * veon_vit_attention_bias_fwd_lse: out = softmax(scale q k^T + bias) v and
+ * lse[b][h][q] = log2 sum_k exp2((scale q.k + bias) log2(e)).
+ *
+ * veon_vit_attention_bias_bwd: dqkv as veon_vit_attention_bwd gives it, and
+ * dbias[B][H][Tb][Tb] (fp32, always dense, also for a broadcast bias: the caller sums)
+ * = dS = P o (dP - delta), the gradient with respect to the bias (no `scale` factor).
+ * Every element of both is written exactly once; no atomics, no memset.  dbias == NULL
+ * skips its stores.  The delta pass of this pair is delta[q] = sum_k P dP / sum_k P from
+ * the rebuilt probabilities themselves (one more sweep over the keys), not
+ * rowsum(dout * out): on the saturated rows a bias with a large diagonal makes, the half
+ * rounding of `out` would be several times the row's whole dS.  `out` is part of the
+ * interface (it is what the forward saved, as in the unbiased pair) and must be valid, but
+ * is not read.  dqkv == NULL (nothing upstream of the qkv Linear needs a gradient) runs
+ * only the delta pass and the dS pass: no dq accumulation, no dk / dv launch.  Both NULL
+ * is VEON_ERR_BAD_ARG.  dqkv and dbias must not alias an input.
+ *
+ * Masks: a bias of -inf gives the key p = 0, ds = 0, dbias = 0.  A query whose keys are
+ * ALL masked has an out row of zeros (as the inference kernel gives) and lse = +inf, so
+ * that the backward's exp2(... - lse) is exactly 0 for it: its dq row and its dbias row are
+ * zero, it adds nothing to any dk or dv, and nothing is NaN.
+ */
+int veon_vit_attention_bias_fwd_lse(const void *qkv, const float *bias, int64_t bias_sb,
+                                    int64_t bias_sh, int border, void *out, float *lse,
+                                    int B, int T, int H, int head_dim, float scale,
+                                    void *stream);
+int veon_vit_attention_bias_bwd(const void *qkv, const float *bias, int64_t bias_sb,
+                                int64_t bias_sh, int border, const void *out,
+                                const void *dout, const float *lse, void *dqkv,
+                                float *dbias, void *workspace, int64_t workspace_bytes,
+                                int B, int T, int H, int head_dim, float scale,
+                                void *stream);
 
 /* ======== temporal_train.hip ======================================================== */
 

@@ -61,10 +61,20 @@ __device__ __forceinline__ float max_over_rows(float x) {
 // in fp32 from the weights before their half rounding (out keeps the matrix core's sum
 // of the rounded ones: it is the inference kernel's to the bit).  The
 // other instantiations ignore the three trailing arguments.
+//
+// STATS with HAS_BIAS (the CLIP tail under autograd): the bias of a (b, h) pair is a
+// [Tb][Tb] matrix, Tb = T - border, rows Tb floats long.  With ``border`` = 1 it is the
+// patch-to-patch matrix: token 0 has bias 0 as a query and as a key BY INDEX (bias element
+// [q - 1][k - 1] for q, k >= 1), and nothing outside the matrix is read.  The inference
+// instantiations ignore ``border``.  A query whose keys are all masked (bias -inf) gets an
+// out row of zeros, as at inference, and lse = +inf: the backward's
+// exp2(s c + bias log2(e) - lse) is then exp2(-inf) = 0, never inf - inf.  This
+// instantiation holds a tile's 64 bias values next to the statistics: it is compiled for two
+// workgroups per CU (at three it spilled 25 registers); the others keep three.
 template <bool HAS_BIAS, bool LOG2Q, bool STATS = false>
-__global__ __launch_bounds__(256, 3) void k_attention(
+__global__ __launch_bounds__(256, (HAS_BIAS && STATS) ? 2 : 3) void k_attention(
     const bf16_t* __restrict__ qkv, const float* __restrict__ bias,
-    int64_t bias_sb, int64_t bias_sh, bf16_t* __restrict__ out, int T, int H,
+    int64_t bias_sb, int64_t bias_sh, int border, bf16_t* __restrict__ out, int T, int H,
     float c_scale, float* __restrict__ lse, int Tp) {
   static_assert(!STATS || !LOG2Q, "the statistics form scales the scores itself");
   __shared__ __attribute__((aligned(16))) bf16_t smem[4 * KV_ELEMS];  // [buf][K|V]
@@ -141,11 +151,16 @@ __global__ __launch_bounds__(256, 3) void k_attention(
 #pragma unroll
   for (int e = 0; e < 8; ++e) ones[e] = f2bf(1.f);
   const float* brow[QT];
+  bool bq[QT];   // STATS: the query has a bias row (it is not the bordered class token)
+  const int bd = STATS ? border : 0;
   if (HAS_BIAS) {
 #pragma unroll
     for (int i = 0; i < QT; ++i) {
       const int q = q0 + i * 16 + fr;
-      brow[i] = bias + b * bias_sb + h * bias_sh + (int64_t)(q < T ? q : T - 1) * T;
+      const int qr = (q < T ? q : T - 1) - bd;
+      bq[i] = qr >= 0;
+      brow[i] = bias + b * bias_sb + h * bias_sh +
+                (int64_t)(STATS && qr < 0 ? 0 : qr) * (T - bd);
     }
   }
   // fragment read offsets (bf16 elements) inside a tile
@@ -210,7 +225,12 @@ __global__ __launch_bounds__(256, 3) void k_attention(
           for (int r = 0; r < 4; ++r) {
             int key = k0 + kt * 16 + fg * 4 + r;
             if (TAIL) key = key < T ? key : T - 1;
-            s[i][kt][r] = fmaf(brow[i][key], kLog2e, s[i][kt][r]);
+            float bv;
+            if (STATS)   // bordered: element [q - 1][key - 1], zero for token 0
+              bv = (bq[i] && key >= bd) ? brow[i][key - bd] : 0.f;
+            else
+              bv = brow[i][key];
+            s[i][kt][r] = fmaf(bv, kLog2e, s[i][kt][r]);
           }
       }
       if (TAIL) {
@@ -346,8 +366,11 @@ __global__ __launch_bounds__(256, 3) void k_attention(
       float lf = lsum[i][0] + lsum[i][1];
       lf += __shfl_xor(lf, 16);
       lf += __shfl_xor(lf, 32);
-      if (q < T && fg == 0)
-        lse[((int64_t)b * H + h) * Tp + q] = __builtin_amdgcn_logf(lf) - negm[i];
+      if (q < T && fg == 0) {
+        float l2 = __builtin_amdgcn_logf(lf) - negm[i];
+        if (HAS_BIAS && lf == 0.f) l2 = INFINITY;   // every key masked
+        lse[((int64_t)b * H + h) * Tp + q] = l2;
+      }
     }
     if (q >= T) continue;
     const float inv = l > 0.f ? 1.f / l : 0.f;

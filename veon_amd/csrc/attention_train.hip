@@ -1,9 +1,10 @@
-// Attention for training (head dim 64, no additive bias): the forward that also records
-// the softmax statistics, and the backward.
+// Attention for training (head dim 64, with or without a dense additive bias): the forward
+// that also records the softmax statistics, and the backward.
 //
 //   k_attention<false, false, true>   attention_kernel.h: the inference kernel with the
 //                     score scale as an argument and lse[b][h][q] written next to out
-//   k_attention_delta delta[b][h][q] = sum_d dO[q][d] * O[q][d], fp32
+//   k_attention<true, false, true>    the same with the fp32 bias added to the scaled scores
+//   k_attention_delta delta[b][h][q] = sum_d dO[q][d] * O[q][d], fp32 (the unbiased pair)
 //   k_attention_bwd<false>   dQ: a wave owns 32 queries, K / V tiles stream through LDS
 //   k_attention_bwd<true>    dK and dV: a wave owns 32 keys, Q / dO tiles stream
 //
@@ -28,6 +29,29 @@
 // clamped on load too and never stored; a column of an MFMA result depends on that
 // column of the B operand alone, so they touch nothing else.
 // Layouts, DMA map, swizzle and fragment reads are those of k_attention.
+//
+// HAS_BIAS (the CLIP tail): p = exp2(s * scale * log2(e) + bias[query][key] * log2(e) - lse),
+// the bias addressed as in k_attention (``border``: token 0 has bias 0 by index; loads are
+// clamped like the rows).  The dQ kernel visits every (query, key) pair exactly once and
+// stores ds to dbias[b][h][query - border][key - border] (dense, no scale factor, skipped
+// when dbias is NULL).  A masked key (bias -inf) has p = ds = 0; a query whose keys are all
+// masked has lse = +inf, so its whole row of p and ds is exp2(-inf) = 0.
+// MODE (dQ kernel with a bias only):
+//   kBwdFull    as above
+//   kBwdDsOnly  nothing upstream of qkv needs a gradient: the dQ accumulation and its stores
+//               are left out and the pass only writes dbias
+//   kBwdDelta   the biased pair's delta pass: delta[b][h][q] = sum_k p dp / sum_k p, fp32
+//               from the unrounded p and dp, written to the workspace for the two passes
+//               after it.  (The division by the sum of the REBUILT p, 1 within the 1e-6 of
+//               the fp32 exponent and the hardware exp2 / log2, makes sum_k dS = 0 hold
+//               for the p the passes use, as softmax's own backward has it; a fully masked
+//               query has delta 0.)
+//               k_attention_delta's dO . O carries the half rounding of O, u |dO . O|; on
+//               the saturated rows a Gram-shaped bias makes (p of the own key within 1e-4
+//               of 1) that is several times the row's whole dS, which p (dp - sum p dp)
+//               gets right because the large own-key term cancels exactly (measured at
+//               (2, 33, 2) in bf16: dq 1.5e-2 from dO . O, 2.2e-3 from sum p dp, against
+//               2.9e-3 of torch's half arithmetic).
 #include "attention_kernel.h"
 
 namespace {
@@ -58,11 +82,18 @@ __global__ __launch_bounds__(256) void k_attention_delta(
   }
 }
 
-template <bool DKV>
+constexpr float kLog2eF = 1.4426950408889634f;
+enum { kBwdFull = 0, kBwdDsOnly = 1, kBwdDelta = 2 };
+
+template <bool DKV, bool HAS_BIAS = false, int MODE = kBwdFull>
 __global__ __launch_bounds__(256, 2) void k_attention_bwd(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
-    bf16_t* __restrict__ dqkv, int T, int H, int Tp, float c_scale, float scale) {
+    bf16_t* __restrict__ dqkv, int T, int H, int Tp, float c_scale, float scale,
+    const float* __restrict__ bias, int64_t bias_sb, int64_t bias_sh, int border,
+    float* __restrict__ dbias, float* __restrict__ delta_out) {
+  static_assert(MODE == kBwdFull || (HAS_BIAS && !DKV), "modes of the biased dQ kernel");
+  constexpr bool GRAD = MODE == kBwdFull, DELTA = MODE == kBwdDelta;
   __shared__ __attribute__((aligned(16))) bf16_t smem[4 * KV_ELEMS];  // [buf][X|Y]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -104,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_bwd(
 
   // own fragments (B operands): lane holds x[row = fr][d = 32 ks + 8fg + j]
   bf16x8 xf[QT][2], yf[QT][2];
-  float lse_o[QT], del_o[QT];
+  float lse_o[QT], del_o[QT], psum[QT];
 #pragma unroll
   for (int i = 0; i < QT; ++i) {
     const int r = r0 + i * 16 + fr;
@@ -118,7 +149,24 @@ __global__ __launch_bounds__(256, 2) void k_attention_bwd(
     }
     if (!DKV) {
       lse_o[i] = lrow[rc];
-      del_o[i] = drow[rc];
+      del_o[i] = DELTA ? 0.f : drow[rc];   // (the delta pass: the running sum p dp)
+      psum[i] = 0.f;
+    }
+  }
+  // bias: own index (row of the matrix in the dQ kernel, column in the dKV kernel), clamped
+  // into [0, Tb); own_b: the own token is not the bordered class token
+  const int Tb = T - border;
+  const float* bmat = nullptr;
+  int own_i[QT];
+  bool own_b[QT];
+  if (HAS_BIAS) {
+    bmat = bias + b * bias_sb + h * bias_sh;
+#pragma unroll
+    for (int i = 0; i < QT; ++i) {
+      const int r = r0 + i * 16 + fr;
+      const int ro = (r < T ? r : T - 1) - border;
+      own_b[i] = ro >= 0;
+      own_i[i] = ro < 0 ? 0 : ro;
     }
   }
   // accumulators, transposed: acc[i][jt][reg] = grad[own row i*16 + fr][d = jt*16 + 4fg + reg]
@@ -178,16 +226,48 @@ __global__ __launch_bounds__(256, 2) void k_attention_bwd(
         for (int r = 0; r < 4; ++r) {
           const float l = DKV ? L4[r] : lse_o[i];
           const float dl = DKV ? D4[r] : del_o[i];
-          float p = __builtin_amdgcn_exp2f(fmaf(s[i][kt][r], c_scale, -l));
+          float e = fmaf(s[i][kt][r], c_scale, -l);
+          if (HAS_BIAS) {
+            int ks = k0 + kt * 16 + 4 * fg + r;
+            if (TAIL) ks = ks < T ? ks : T - 1;
+            ks -= border;
+            float bv = 0.f;
+            if (own_b[i] && ks >= 0)
+              bv = DKV ? bmat[(int64_t)ks * Tb + own_i[i]] : bmat[(int64_t)own_i[i] * Tb + ks];
+            e = fmaf(bv, kLog2eF, e);
+          }
+          float p = __builtin_amdgcn_exp2f(e);
           float ds = p * (dp[i][kt][r] - dl);
           if (TAIL && k0 + kt * 16 + 4 * fg + r >= T) {
             p = 0.f;
             ds = 0.f;
           }
+          if (DELTA) {
+            del_o[i] = fmaf(p, dp[i][kt][r], del_o[i]);
+            psum[i] += p;
+          }
           s[i][kt][r] = p;
           dp[i][kt][r] = ds;
         }
     }
+    if (DELTA) return;
+    if (HAS_BIAS && !DKV && dbias != nullptr) {
+      // every (query, key) pair of the matrix once: 16 bytes per lane and key tile
+#pragma unroll
+      for (int i = 0; i < QT; ++i) {
+        const int q = r0 + i * 16 + fr;
+        if (q >= T || q < border) continue;
+        float* drow_b = dbias + (((int64_t)b * H + h) * Tb + (q - border)) * Tb;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int key = k0 + kt * 16 + 4 * fg + r;
+            if ((!TAIL || key < T) && key >= border) drow_b[key - border] = dp[i][kt][r];
+          }
+      }
+    }
+    if (!GRAD) return;
     // acc^T += X^T ds (and Y^T p): MFMA k-slot (8fg + j) <-> streamed row
     //   j < 4 : row tile 2*kk,   rows 4fg + j
     //   j >= 4: row tile 2*kk+1, rows 4fg + (j-4)
@@ -240,6 +320,20 @@ __global__ __launch_bounds__(256, 2) void k_attention_bwd(
     }
     __syncthreads();  // next tile landed, this one fully consumed
   }
+  if (DELTA) {
+    // the four lane rows of a query hold 16 keys of every tile each: added in a fixed order
+#pragma unroll
+    for (int i = 0; i < QT; ++i) {
+      float d = del_o[i], l = psum[i];
+      d += __shfl_xor(d, 16);
+      d += __shfl_xor(d, 32);
+      l += __shfl_xor(l, 16);
+      l += __shfl_xor(l, 32);
+      const int r = r0 + i * 16 + fr;
+      if (r < T && fg == 0) delta_out[((int64_t)b * H + h) * Tp + r] = l > 0.f ? d / l : 0.f;
+    }
+  }
+  if (!GRAD) return;
   // store: lane owns grad[row = fr][d = j*16 + 4fg .. +3]; q and k thirds times scale
 #pragma unroll
   for (int i = 0; i < QT; ++i) {
@@ -261,12 +355,19 @@ __global__ __launch_bounds__(256, 2) void k_attention_bwd(
   }
 }
 
-constexpr float kLog2eF = 1.4426950408889634f;
-
 bool att_shape_ok(int B, int T, int H, int head_dim) {
   // the tile DMA addresses an image's rows with 32-bit byte offsets
   return B > 0 && T > 0 && H > 0 && head_dim == HD &&
          (int64_t)T * 3 * H * HD * 2 < (1ll << 31) && B <= 65535 && H <= 65535;
+}
+
+// the bias of the biased pair: fp32 [.][.][Tb][Tb], Tb = T - border, strides >= 0; with
+// Tb == 0 (T = 1, border = 1) it is never read and may be NULL
+bool bias_ok(const float* bias, int64_t sb, int64_t sh, int border, int T) {
+  if (border != 0 && border != 1) return false;
+  if (sb < 0 || sh < 0) return false;
+  if (T - border == 0) return true;
+  return bias != nullptr && (uintptr_t)bias % 4 == 0;
 }
 
 }  // namespace
@@ -285,7 +386,7 @@ int veon_vit_attention_fwd_lse(const void* qkv, void* out, float* lse, int B, in
   const dim3 grid((unsigned)((T + 4 * AQ - 1) / (4 * AQ)), (unsigned)H, (unsigned)B);
   hipLaunchKernelGGL((k_attention<false, false, true>), grid, dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
-                     static_cast<const float*>(nullptr), (int64_t)0, (int64_t)0,
+                     static_cast<const float*>(nullptr), (int64_t)0, (int64_t)0, 0,
                      static_cast<bf16_t*>(out), T, H, scale * kLog2eF, lse,
                      (int)veon_vit_attention_stats_len(T));
   return launch_status();
@@ -322,9 +423,72 @@ int veon_vit_attention_bwd(const void* qkv, const void* out, const void* dout,
   const dim3 grid((unsigned)((T + 4 * AQ - 1) / (4 * AQ)), (unsigned)H, (unsigned)B);
   const float c = scale * kLog2eF;
   hipLaunchKernelGGL((k_attention_bwd<false>), grid, dim3(256), 0, s, q, go, lse, delta,
-                     static_cast<bf16_t*>(dqkv), T, H, Tp, c, scale);
+                     static_cast<bf16_t*>(dqkv), T, H, Tp, c, scale,
+                     static_cast<const float*>(nullptr), (int64_t)0, (int64_t)0, 0,
+                     static_cast<float*>(nullptr), static_cast<float*>(nullptr));
   hipLaunchKernelGGL((k_attention_bwd<true>), grid, dim3(256), 0, s, q, go, lse, delta,
-                     static_cast<bf16_t*>(dqkv), T, H, Tp, c, scale);
+                     static_cast<bf16_t*>(dqkv), T, H, Tp, c, scale,
+                     static_cast<const float*>(nullptr), (int64_t)0, (int64_t)0, 0,
+                     static_cast<float*>(nullptr), static_cast<float*>(nullptr));
+  return launch_status();
+}
+
+int veon_vit_attention_bias_fwd_lse(const void* qkv, const float* bias, int64_t bias_sb,
+                                    int64_t bias_sh, int border, void* out, float* lse, int B,
+                                    int T, int H, int head_dim, float scale, void* stream) {
+  if (!qkv || !out || !lse || !att_shape_ok(B, T, H, head_dim) || !(scale > 0.f) ||
+      !bias_ok(bias, bias_sb, bias_sh, border, T))
+    return VEON_ERR_BAD_ARG;
+  if (!al16(qkv) || !al16(out) || !al16(lse)) return VEON_ERR_BAD_ARG;
+  const dim3 grid((unsigned)((T + 4 * AQ - 1) / (4 * AQ)), (unsigned)H, (unsigned)B);
+  hipLaunchKernelGGL((k_attention<true, false, true>), grid, dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv), bias,
+                     bias_sb, bias_sh, border, static_cast<bf16_t*>(out), T, H,
+                     scale * kLog2eF, lse, (int)veon_vit_attention_stats_len(T));
+  return launch_status();
+}
+
+int veon_vit_attention_bias_bwd(const void* qkv, const float* bias, int64_t bias_sb,
+                                int64_t bias_sh, int border, const void* out, const void* dout,
+                                const float* lse, void* dqkv, float* dbias, void* workspace,
+                                int64_t workspace_bytes, int B, int T, int H, int head_dim,
+                                float scale, void* stream) {
+  if (!qkv || !out || !dout || !lse || (!dqkv && !dbias) || !workspace ||
+      !att_shape_ok(B, T, H, head_dim) || !(scale > 0.f) ||
+      !bias_ok(bias, bias_sb, bias_sh, border, T))
+    return VEON_ERR_BAD_ARG;
+  if (dqkv && (dqkv == qkv || dqkv == out || dqkv == dout || !al16(dqkv)))
+    return VEON_ERR_BAD_ARG;
+  if (dbias && ((uintptr_t)dbias % 4 != 0 || dbias == bias)) return VEON_ERR_BAD_ARG;
+  if (!al16(qkv) || !al16(out) || !al16(dout) || !al16(lse) || !al16(workspace))
+    return VEON_ERR_BAD_ARG;
+  if (workspace_bytes < veon_vit_attention_bwd_workspace_bytes(B, T, H))
+    return VEON_ERR_WORKSPACE;
+  const int Tp = (int)veon_vit_attention_stats_len(T);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* delta = static_cast<float*>(workspace);
+  const bf16_t* q = static_cast<const bf16_t*>(qkv);
+  const bf16_t* go = static_cast<const bf16_t*>(dout);
+  bf16_t* dq = static_cast<bf16_t*>(dqkv);
+  const dim3 grid((unsigned)((T + 4 * AQ - 1) / (4 * AQ)), (unsigned)H, (unsigned)B);
+  const float c = scale * kLog2eF;
+  float* none = nullptr;
+  // delta = sum_k p dp from the probabilities themselves (see kBwdDelta above)
+  hipLaunchKernelGGL((k_attention_bwd<false, true, kBwdDelta>), grid, dim3(256), 0, s, q, go,
+                     lse, delta, dq, T, H, Tp, c, scale, bias, bias_sb, bias_sh, border, none,
+                     delta);
+  if (dq) {
+    hipLaunchKernelGGL((k_attention_bwd<false, true, kBwdFull>), grid, dim3(256), 0, s, q, go,
+                       lse, delta, dq, T, H, Tp, c, scale, bias, bias_sb, bias_sh, border,
+                       dbias, none);
+    hipLaunchKernelGGL((k_attention_bwd<true, true, kBwdFull>), grid, dim3(256), 0, s, q, go,
+                       lse, delta, dq, T, H, Tp, c, scale, bias, bias_sb, bias_sh, border, none,
+                       none);
+  } else {
+    hipLaunchKernelGGL((k_attention_bwd<false, true, kBwdDsOnly>), grid, dim3(256), 0, s, q,
+                       go, lse, delta, dq, T, H, Tp, c, scale, bias, bias_sb, bias_sh, border,
+                       dbias, none);
+  }
   return launch_status();
 }
 

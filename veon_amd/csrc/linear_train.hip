@@ -64,8 +64,9 @@ __global__ __launch_bounds__(256) void k_rows_colsum(const bf16_t* __restrict__ 
 }
 
 // h = GELU(y), or dy = dh GELU'(y): one 16-byte chunk per thread, fp32 from the stored
-// half value, both from the one erfc evaluation of gelu_and_slope.
-template <bool BWD>
+// half value, both from the one erfc evaluation of gelu_and_slope.  QUICK: CLIP's
+// QuickGELU y sigma(1.702 y) and its slope sigma + 1.702 y sigma (1 - sigma).
+template <bool BWD, bool QUICK = false>
 __global__ __launch_bounds__(256) void k_gelu(const bf16_t* __restrict__ y,
                                               const bf16_t* __restrict__ dh,
                                               bf16_t* __restrict__ out, int64_t n8) {
@@ -77,7 +78,14 @@ __global__ __launch_bounds__(256) void k_gelu(const bf16_t* __restrict__ y,
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     float g, slope;
-    gelu_and_slope(bf2f((bf16_t)c[k]), &g, &slope);
+    if (QUICK) {
+      const float yv = bf2f((bf16_t)c[k]);
+      const float sg = 1.f / (1.f + __expf(-1.702f * yv));
+      g = yv * sg;
+      slope = sg + 1.702f * yv * sg * (1.f - sg);
+    } else {
+      gelu_and_slope(bf2f((bf16_t)c[k]), &g, &slope);
+    }
     o[k] = (short)f2bf(BWD ? bf2f((bf16_t)d[k]) * slope : g);
   }
   reinterpret_cast<bf16x8*>(out)[i] = o;
@@ -238,6 +246,26 @@ int veon_gelu_bwd_bf16(const void* dh, const void* y, void* dy, int64_t n, void*
       !al16(y) || !al16(dy))
     return VEON_ERR_BAD_ARG;
   hipLaunchKernelGGL((k_gelu<true>), dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(y),
+                     static_cast<const bf16_t*>(dh), static_cast<bf16_t*>(dy), n / 8);
+  return launch_status();
+}
+
+int veon_quickgelu_bf16(const void* y, void* h, int64_t n, void* stream) {
+  if (n <= 0 || n % 8 != 0 || n / 8 > 0x7fffffffLL * 256 || !y || !h || !al16(y) || !al16(h))
+    return VEON_ERR_BAD_ARG;
+  hipLaunchKernelGGL((k_gelu<false, true>), dim3((unsigned)((n / 8 + 255) / 256)), dim3(256),
+                     0, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(y),
+                     static_cast<const bf16_t*>(nullptr), static_cast<bf16_t*>(h), n / 8);
+  return launch_status();
+}
+
+int veon_quickgelu_bwd_bf16(const void* dh, const void* y, void* dy, int64_t n,
+                            void* stream) {
+  if (n <= 0 || n % 8 != 0 || n / 8 > 0x7fffffffLL * 256 || !dh || !y || !dy || !al16(dh) ||
+      !al16(y) || !al16(dy))
+    return VEON_ERR_BAD_ARG;
+  hipLaunchKernelGGL((k_gelu<true, true>), dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(y),
                      static_cast<const bf16_t*>(dh), static_cast<bf16_t*>(dy), n / 8);
   return launch_status();

@@ -1416,7 +1416,7 @@ static int attention_launch(const void* qkv_bf16, const float* bias,
   hipLaunchKernelGGL((k_attention<BIAS, LOG2Q>), grid, dim3(256), 0,           \
                      static_cast<hipStream_t>(stream),                         \
                      static_cast<const bf16_t*>(qkv_bf16), bias,               \
-                     bias_batch_stride, bias_head_stride,                      \
+                     bias_batch_stride, bias_head_stride, 0,                   \
                      static_cast<bf16_t*>(out_bf16), T, H, 0.f,                \
                      static_cast<float*>(nullptr), 0)
   if (q_log2) {

@@ -84,6 +84,21 @@ class _GeluFn(torch.autograd.Function):
         return vit_ops.gelu_bwd(dh.contiguous(), y)
 
 
+class _QuickGeluFn(torch.autograd.Function):
+    """CLIP's QuickGELU on half rows from the saved pre-activation."""
+
+    @staticmethod
+    def forward(ctx, y):
+        ctx.save_for_backward(y)
+        return vit_ops.quickgelu(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh):
+        y, = ctx.saved_tensors
+        return vit_ops.quickgelu_bwd(dh.contiguous(), y)
+
+
 class _FFHiddenFn(torch.autograd.Function):
     """The first half of ``FeedForward`` for training (csrc/linear_train.hip): fp32 tokens
     x -> h = GELU(LN(x) W1^T + b1), half.  Saved for backward: x, the half rows LN(x) and the

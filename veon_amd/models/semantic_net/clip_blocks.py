@@ -29,6 +29,7 @@ import torch.nn.functional as F
 
 from ... import vit_ops
 from .._native_cache import NativeCacheMixin
+from .._train_fns import _GeluFn, _LinearTrainFn, _LNHalfFn, _QuickGeluFn
 from .resize import interpolate
 
 
@@ -37,7 +38,38 @@ class QuickGELU(nn.Module):
         return x * torch.sigmoid(1.702 * x)
 
 
+def _ln_train_ok(ln, d):
+    return (type(ln) is nn.LayerNorm and tuple(ln.normalized_shape) == (d,)
+            and ln.weight is not None and ln.bias is not None
+            and ln.weight.dtype == torch.float32 and ln.bias.dtype == torch.float32)
+
+
+def _mask_train_ok(m, N, H, L):
+    """None, or a floating additive mask (N, H, Lb, Lb) with unit-size batch / head axes
+    allowed, (N*H, Lb, Lb) or (Lb, Lb), Lb = L (with the class token) or L - 1 (without)."""
+    if m is None:
+        return True
+    if not (torch.is_tensor(m) and m.is_cuda and m.dtype == torch.float32
+            and m.dim() in (2, 3, 4) and m.shape[-1] == m.shape[-2]
+            and m.shape[-1] in (L, L - 1)):
+        return False
+    if m.dim() == 3:
+        return m.shape[0] == N * H
+    return m.dim() == 2 or (m.shape[0] in (1, N) and m.shape[1] in (1, H))
+
+
 class ResidualAttentionBlock(nn.Module):
+    """``hip_train`` (class attribute, default False): opt-in native TRAINING path.  When
+    set, a block under autograd on ROCm fp32 tokens whose shapes the kernels take
+    (``_hip_train_ok``) runs its LayerNorms, the four Linears, the attention with its dense
+    additive mask (csrc/attention_train.hip: the only T x T tensor saved is the mask it was
+    handed, and the mask receives its gradient) and the activation, forward and backward, in
+    HIP on half rows; the residual adds stay in torch on the fp32 stream.  The block has no
+    dropout and no batch statistics, so unlike the other ``hip_train`` switches this one
+    does NOT depend on ``.training``.  Anything else takes ``forward``'s lines unchanged."""
+
+    hip_train = False
+
     def __init__(self, d_model, n_head, mlp_ratio=4.0, quick_gelu=True):
         super().__init__()
         self.ln_1 = nn.LayerNorm(d_model)
@@ -53,9 +85,64 @@ class ResidualAttentionBlock(nn.Module):
         self.n_head = n_head
         self.quick_gelu = quick_gelu
 
+    def _hip_train_ok(self, x, attn_mask=None):
+        """The native training path's own test: the switch, autograd, ROCm fp32 tokens
+        (L, N, D), D % 64 == 0, head dim 64, D <= 1024 (the LayerNorm backward), MLP width
+        % 64 == 0, affine fp32 LayerNorms, QuickGELU or exact
+        GELU, identity ``ls_1`` / ``ls_2``, fp32 parameters, an nn.MultiheadAttention with
+        its packed in_proj and an out_proj with bias and no dropout, and a mask that is None
+        or a floating additive one of the three shapes.  Not ``.training``: see the class."""
+        if not (self.hip_train and torch.is_grad_enabled() and torch.is_tensor(x)
+                and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
+                and type(self.attn) is nn.MultiheadAttention
+                and type(self.mlp) is nn.Sequential and len(self.mlp) == 3):
+            return False
+        a, d = self.attn, x.shape[-1]
+        L, N = x.shape[:2]
+        fc, act, pr = self.mlp[0], self.mlp[1], self.mlp[2]
+        return (d % 64 == 0 and d <= 1024 and a.embed_dim == d and d == a.num_heads * 64
+                and a.num_heads == self.n_head
+                and a.in_proj_weight is not None and a.in_proj_bias is not None
+                and a._qkv_same_embed_dim and a.dropout == 0.0 and not a.batch_first
+                and a.bias_k is None and a.bias_v is None and not a.add_zero_attn
+                and isinstance(a.out_proj, nn.Linear) and a.out_proj.bias is not None
+                and type(fc) is nn.Linear and type(pr) is nn.Linear
+                and fc.bias is not None and pr.bias is not None
+                and fc.in_features == d and fc.out_features % 64 == 0
+                and pr.in_features == fc.out_features and pr.out_features == d
+                and _ln_train_ok(self.ln_1, d) and _ln_train_ok(self.ln_2, d)
+                and (type(act) is QuickGELU
+                     or (type(act) is nn.GELU and getattr(act, 'approximate', 'none') == 'none'))
+                and type(self.ls_1) is nn.Identity and type(self.ls_2) is nn.Identity
+                and all(p.dtype == torch.float32 and p.is_cuda for p in self.parameters())
+                and _mask_train_ok(attn_mask, N, a.num_heads, L))
+
+    def _hip_train_forward(self, x, attn_mask=None):
+        """The native step on BATCH-MAJOR fp32 tokens x (N, L, D) -> (N, L, D)."""
+        N, L, d = x.shape
+        a, n1, n2 = self.attn, self.ln_1, self.ln_2
+        fc, act, pr = self.mlp[0], self.mlp[1], self.mlp[2]
+        scale = (d // a.num_heads) ** -0.5
+        xn = _LNHalfFn.apply(x, n1.weight, n1.bias, n1.eps)              # half [N*L, d]
+        qkv = _LinearTrainFn.apply(xn, a.in_proj_weight, a.in_proj_bias).view(N, L, 3 * d)
+        if attn_mask is None:
+            o = vit_ops.attention_train(qkv, a.num_heads, scale)         # raw q: no scale
+        else:
+            o = vit_ops.attention_bias_train(qkv, attn_mask, a.num_heads, scale,
+                                             border=L - attn_mask.shape[-1])
+        y = _LinearTrainFn.apply(o.view(N * L, d), a.out_proj.weight, a.out_proj.bias)
+        x = x + y.view(N, L, d).float()
+        xn = _LNHalfFn.apply(x, n2.weight, n2.bias, n2.eps)
+        h = _LinearTrainFn.apply(xn, fc.weight, fc.bias)
+        h = (_QuickGeluFn if type(act) is QuickGELU else _GeluFn).apply(h)
+        y = _LinearTrainFn.apply(h, pr.weight, pr.bias)
+        return x + y.view(N, L, d).float()
+
     def forward(self, x, attn_mask=None):
         """x (L, N, D) sequence-first, attn_mask additive (N*heads, L, L) or
         (L, L), as open_clip passes it."""
+        if self._hip_train_ok(x, attn_mask):
+            return self._hip_train_forward(x.permute(1, 0, 2), attn_mask).permute(1, 0, 2)
         h = self.ln_1(x)
         a = self.attn(h, h, h, need_weights=False, attn_mask=attn_mask)[0]
         x = x + self.ls_1(a)
@@ -145,17 +232,43 @@ def hip_blocks_ok(blocks, x, D):
             and D % 64 == 0 and all(D // b.n_head == 64 for b in blocks))
 
 
-def run_blocks(blocks, x_lnd, attn_masks=None, cache=None, keep=None, stream=None):
+def hip_train_blocks_ok(blocks, x_lnd, attn_masks=None):
+    """The condition of run_blocks' native training path: the inference path does not
+    apply and every block passes its ``_hip_train_ok`` with its mask.  The switch is read
+    first, so that with it off (the default) a call costs one attribute read per block."""
+    if not blocks or not all(getattr(b, 'hip_train', False) for b in blocks) \
+            or hip_blocks_ok(blocks, x_lnd, x_lnd.shape[-1]):
+        return False
+    return all(b._hip_train_ok(x_lnd, None if attn_masks is None else attn_masks[i])
+               for i, b in enumerate(blocks))
+
+
+def run_blocks(blocks, x_lnd, attn_masks=None, cache=None, keep=None, stream=None,
+               train_native=None):
     """Run ``blocks`` over x (L, N, D).  On a ROCm device in no-grad eval mode
-    the MFMA kernels are used (one transpose in, one out); otherwise the torch
+    the MFMA kernels are used (one transpose in, one out); under autograd with
+    ``ResidualAttentionBlock.hip_train`` set and every block passing ``_hip_train_ok``, the
+    native training path (batch-major, one transpose in, every output handed back as an
+    (L, N, D) view whatever ``keep`` says; a mask whose last axis is L - 1 is the
+    patch-to-patch bias and goes to the kernel with ``border`` = 1); otherwise the torch
     blocks.  attn_masks: None or one additive mask per block, each
     (N*heads, L, L) / (N, heads, L, L) / (L, L).  Returns the list of per-block
     outputs (L, N, D).  ``keep``: indices of the blocks whose output the caller reads
     (the last one always is); the native path leaves the others as None instead of
-    copying the stream out after every block."""
+    copying the stream out after every block.  ``train_native``: a caller that has already
+    evaluated ``hip_train_blocks_ok`` for these arguments hands its answer over; None
+    evaluates it here."""
     L, N, D = x_lnd.shape
-    hip = hip_blocks_ok(blocks, x_lnd, D)
+    if train_native is None:
+        train_native = hip_train_blocks_ok(blocks, x_lnd, attn_masks)
+    hip = not train_native and hip_blocks_ok(blocks, x_lnd, D)
     outs = []
+    if train_native:
+        x = x_lnd.permute(1, 0, 2).contiguous()
+        for i, blk in enumerate(blocks):
+            x = blk._hip_train_forward(x, None if attn_masks is None else attn_masks[i])
+            outs.append(x.permute(1, 0, 2))
+        return outs
     if not hip:
         x = x_lnd
         for i, blk in enumerate(blocks):
@@ -457,12 +570,20 @@ class ClipRecHead(NativeCacheMixin, nn.Module):
             # (biases that already carry the class token's zero row / column --
             # AttnManipulateBlock.pad_class_token -- pass through)
             L1 = x.shape[0]
-            masks = None if attns is None else \
-                [attns[t].reshape(-1, L1, L1) if attns[t].shape[-1] == L1
-                 else self.build_attn_bias(attns[t]) for t in range(a, b)]
+            blocks = list(self.resblocks)[a:b]
+            native = attns is not None and hip_train_blocks_ok(blocks, x, attns[a:b])
+            if native:
+                # the native training path takes the patch-to-patch matrix as it is: the
+                # class token's zero row / column is the kernel's ``border``
+                masks = list(attns[a:b])
+            else:
+                masks = None if attns is None else \
+                    [attns[t].reshape(-1, L1, L1) if attns[t].shape[-1] == L1
+                     else self.build_attn_bias(attns[t]) for t in range(a, b)]
             keep = None if keep_layers is None else \
                 {t - a for t in range(a, b) if t + k0 + 1 in keep_layers}
-            outs = run_blocks(list(self.resblocks)[a:b], x, masks, self._hip_cache, keep)
+            outs = run_blocks(blocks, x, masks, self._hip_cache, keep,
+                              train_native=None if attns is None else native)
             for t, o in zip(range(a, b), outs):
                 if o is not None and (keep_layers is None or t + k0 + 1 in keep_layers
                                       or t + 1 == nblk):

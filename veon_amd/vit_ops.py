@@ -195,6 +195,33 @@ def gelu_bwd(dh, y):
     return out
 
 
+def quickgelu(y):
+    """CLIP's QuickGELU y * sigmoid(1.702 y) of a half tensor, in fp32 from the stored half
+    value -> half."""
+    dev = _dev(y)
+    _rows(y)
+    out = torch.empty_like(y)
+    _lib.launch('veon_quickgelu_bf16', dev, y, out, y.numel())
+    return out
+
+
+def quickgelu_bwd(dh, y):
+    """dh * (s + 1.702 y s (1 - s)), s = sigmoid(1.702 y), on half tensors -> half."""
+    dev = _dev(dh, y)
+    _rows(y)
+    _rows(dh)
+    assert dh.shape == y.shape
+    out = torch.empty_like(y)
+    _lib.launch('veon_quickgelu_bwd_bf16', dev, dh, y, out, y.numel())
+    return out
+
+
+def quickgelu_bwd_ref(dh, y):
+    """``quickgelu_bwd`` in torch, in the operands' own dtype (pass fp64 for a reference)."""
+    s = torch.sigmoid(1.702 * y)
+    return dh * (s + 1.702 * y * s * (1 - s))
+
+
 def layernorm_f32_bwd(dout, x, gamma, eps):
     """Backward of nn.LayerNorm over the last axis at its stored fp32 input ``x``
     [..., d]; ``dout`` fp32 or half, same shape.  -> (dx fp32, dgamma, dbeta fp32 [d]).
@@ -355,6 +382,192 @@ class _AttentionTrainFn(torch.autograd.Function):
 def attention_train(qkv, num_heads, scale):
     """``attention_fwd_lse``'s out under autograd, backward on ``attention_bwd``."""
     return _AttentionTrainFn.apply(qkv, num_heads, scale)
+
+
+# --------------------------- attention with a dense additive bias, for training (the CLIP tail)
+def _bias_view(bias, B, H, Tb):
+    """A bias (B, H, Tb, Tb) with unit-size batch / head axes allowed, (B*H, Tb, Tb) or
+    (Tb, Tb) as a 4-D VIEW whose last two axes are dense rows of Tb floats -> (view,
+    bias_sb, bias_sh), a zero stride for a broadcast axis.  No copy unless the rows are
+    not dense."""
+    assert bias.dtype == torch.float32 and bias.shape[-2:] == (Tb, Tb)
+    if bias.dim() == 2:
+        v = bias.view(1, 1, Tb, Tb)
+    elif bias.dim() == 3:
+        assert bias.shape[0] == B * H
+        if Tb and (bias.stride(-1) != 1 or bias.stride(-2) != Tb):
+            bias = bias.contiguous()
+        v = bias.reshape(B, H, Tb, Tb)
+    else:
+        assert bias.dim() == 4 and bias.shape[0] in (1, B) and bias.shape[1] in (1, H)
+        v = bias
+    if Tb and (v.stride(-1) != 1 or v.stride(-2) != Tb):
+        v = v.contiguous()
+    sb = v.stride(0) if v.shape[0] > 1 else 0
+    sh = v.stride(1) if v.shape[1] > 1 else 0
+    return v, sb, sh
+
+
+def attention_bias_fwd_lse(qkv, bias, num_heads, scale, border=0, out=None, lse=None):
+    """``attention_fwd_lse`` with an fp32 additive bias (natural-log units, added to
+    scale q.k): (B, H, Tb, Tb) with unit-size axes broadcast, (B*H, Tb, Tb) or (Tb, Tb),
+    Tb = T - border.  ``border`` = 1: the bias is patch-to-patch and token 0 has bias 0 as a
+    query and as a key, by index.  A query whose keys are all masked (-inf) gets an out row
+    of zeros and lse = +inf."""
+    dev = _dev(qkv, bias)
+    B, T, hd = _qkv_dims(qkv, num_heads)
+    assert border in (0, 1)
+    bv, sb, sh = _bias_view(bias, B, num_heads, T - border)
+    if out is None:
+        out = torch.empty((B, T, num_heads * hd), dtype=_half.dtype(), device=dev)
+    if lse is None:
+        lse = torch.empty((B, num_heads, attention_stats_len(T)), dtype=torch.float32,
+                          device=dev)
+    assert lse.is_contiguous() and lse.dtype == torch.float32
+    _lib.launch('veon_vit_attention_bias_fwd_lse', dev, qkv, bv, sb, sh, int(border), out, lse,
+                B, T, num_heads, hd, float(scale))
+    return out, lse
+
+
+def attention_bias_bwd(qkv, bias, out, dout, lse, num_heads, scale, border=0, dqkv=True,
+                       dbias=True, workspace=None):
+    """Backward of ``attention_bias_fwd_lse`` -> (dqkv half like qkv, dbias fp32
+    (B, H, Tb, Tb)): dbias is ALWAYS dense (the caller sums over broadcast axes) and is the
+    gradient with respect to the bias, dS.  ``dqkv`` / ``dbias``: True allocates, a tensor
+    is written into, None skips that gradient (its result is None); without dqkv only the
+    delta pass (here sum_k p dp, a sweep over the keys; ``out`` is not read) and the dS pass
+    run, counted under ``'veon_vit_attention_bias_bwd:ds_only'``
+    in ``_lib.CALLS``.  Every element of both is written; no atomics: deterministic."""
+    dev = _dev(qkv, bias, out, dout, lse)
+    B, T, hd = _qkv_dims(qkv, num_heads)
+    H, Tb = num_heads, T - border
+    assert border in (0, 1) and (dqkv is not None or dbias is not None)
+    _lib.require_half(out, dout)
+    assert out.is_contiguous() and dout.is_contiguous() and out.shape == dout.shape
+    assert out.shape == (B, T, H * hd)
+    Tp = attention_stats_len(T)
+    assert lse.is_contiguous() and lse.dtype == torch.float32 and lse.shape == (B, H, Tp)
+    bv, sb, sh = _bias_view(bias, B, H, Tb)
+    nbytes = int(_lib.lib().veon_vit_attention_bwd_workspace_bytes(B, T, H))
+    if nbytes < 0:
+        raise _lib.VeonHipError('attention_bias_bwd: unsupported shape')
+    if workspace is None:
+        workspace = torch.empty((B, H, Tp), dtype=torch.float32, device=dev)
+    assert workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= nbytes
+    if dqkv is True:
+        dqkv = torch.empty_like(qkv)
+    if dbias is True:
+        dbias = torch.empty((B, H, Tb, Tb), dtype=torch.float32, device=dev)
+    if dqkv is not None:
+        assert dqkv.is_contiguous() and dqkv.shape == qkv.shape and dqkv.dtype == qkv.dtype
+    if dbias is not None:
+        assert dbias.is_contiguous() and dbias.shape == (B, H, Tb, Tb)
+        assert dbias.dtype == torch.float32
+    if dqkv is None:
+        if Tb == 0:          # an empty matrix: nothing to compute
+            return None, dbias
+        _lib.CALLS['veon_vit_attention_bias_bwd:ds_only'] = \
+            _lib.CALLS.get('veon_vit_attention_bias_bwd:ds_only', 0) + 1
+    _lib.launch('veon_vit_attention_bias_bwd', dev, qkv, bv, sb, sh, int(border), out, dout,
+                lse, dqkv, dbias if Tb else None, workspace,
+                workspace.numel() * workspace.element_size(), B, T, H, hd, float(scale))
+    return dqkv, dbias
+
+
+def _full_bias(bias, B, H, T, border):
+    """The bias of any accepted shape as (B, H, T, T); the border by zero padding."""
+    Tb = T - border
+    if bias.dim() == 3:
+        bias = bias.reshape(B, H, Tb, Tb)
+    elif bias.dim() == 2:
+        bias = bias.reshape(1, 1, Tb, Tb)
+    if border:
+        bias = torch.nn.functional.pad(bias, (1, 0, 1, 0))
+    return bias.expand(B, H, T, T)
+
+
+def _masked_softmax(s):
+    """softmax over the last axis; a row of -inf alone gives zeros (torch gives NaN)."""
+    dead = (s == float('-inf')).all(-1, keepdim=True)
+    return torch.where(dead, torch.zeros_like(s), s.masked_fill(dead, 0).softmax(dim=-1))
+
+
+def attention_bias_ref(qkv, bias, num_heads, scale, border=0, dtype=None):
+    """softmax(scale q k^T + bias) v in torch, q k v in ``dtype`` (default: qkv's own; pass
+    fp64 for a reference): the scores are converted to the bias's precision (fp32, or fp64
+    with a double bias) before the bias is added, which is what the kernel does.  A row
+    whose keys are all masked is zero, as in the kernel."""
+    B, T, three_d = qkv.shape
+    x = qkv if dtype is None else qkv.to(dtype)
+    q, k, v = x.reshape(B, T, 3, num_heads, -1).permute(2, 0, 3, 1, 4)
+    full = _full_bias(bias, B, num_heads, T, border)
+    s = ((q * scale) @ k.transpose(-2, -1)).to(full.dtype) + full
+    attn = _masked_softmax(s).to(x.dtype)
+    return (attn @ v).transpose(1, 2).reshape(B, T, three_d // 3)
+
+
+def attention_bias_bwd_ref(qkv, bias, dout, num_heads, scale, border=0, dtype=None):
+    """``attention_bias_bwd`` in torch -> (dqkv [B,T,3*H*hd], dbias dense (B, H, Tb, Tb)):
+    the closed form of ``attention_bwd_ref`` with P = softmax(scale q k^T + bias) and
+    dbias = dS.  A query whose keys are all masked has P = 0 by definition: its rows of
+    dq, dbias are zero and it adds nothing to dk, dv."""
+    B, T, three_d = qkv.shape
+    x = qkv if dtype is None else qkv.to(dtype)
+    q, k, v = x.reshape(B, T, 3, num_heads, -1).permute(2, 0, 3, 1, 4)
+    do = dout.to(x.dtype).reshape(B, T, num_heads, -1).permute(0, 2, 1, 3)
+    full = _full_bias(bias, B, num_heads, T, border)
+    s = ((q * scale) @ k.transpose(-2, -1)).to(full.dtype) + full
+    p = _masked_softmax(s).to(x.dtype)
+    o = p @ v
+    dv = p.transpose(-2, -1) @ do
+    dp = do @ v.transpose(-2, -1)
+    ds = p * (dp - (do * o).sum(-1, keepdim=True))
+    dq = (ds @ k) * scale
+    dk = (ds.transpose(-2, -1) @ q) * scale
+    dqkv = torch.stack((dq, dk, dv)).permute(1, 3, 0, 2, 4).reshape(B, T, three_d)
+    return dqkv, ds[:, :, border:, border:]
+
+
+class _AttentionBiasTrainFn(torch.autograd.Function):
+    """Saves qkv, out, lse and the bias it was handed: no other T x T tensor."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, num_heads, scale, border):
+        qkv = qkv.contiguous()
+        out, lse = attention_bias_fwd_lse(qkv, bias.detach(), num_heads, scale, border)
+        ctx.num_heads, ctx.scale, ctx.border = num_heads, scale, border
+        ctx.save_for_backward(qkv, bias, out, lse)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        qkv, bias, out, lse = ctx.saved_tensors
+        need_qkv, need_bias = ctx.needs_input_grad[:2]
+        if not (need_qkv or need_bias):
+            return None, None, None, None, None
+        dqkv, dbias = attention_bias_bwd(
+            qkv, bias.detach(), out, dout.contiguous(), lse, ctx.num_heads, ctx.scale,
+            ctx.border, dqkv=True if need_qkv else None, dbias=True if need_bias else None)
+        if dbias is not None:
+            B, H = dbias.shape[:2]
+            if bias.dim() == 2:
+                dbias = dbias.sum((0, 1))
+            elif bias.dim() == 3:
+                dbias = dbias.view(bias.shape)
+            else:
+                axes = [a for a in (0, 1) if bias.shape[a] == 1 and dbias.shape[a] > 1]
+                if axes:
+                    dbias = dbias.sum(axes, keepdim=True)
+        return dqkv, dbias, None, None, None
+
+
+def attention_bias_train(qkv, bias, num_heads, scale, border=0):
+    """``attention_bias_fwd_lse``'s out under autograd, backward on ``attention_bias_bwd``:
+    a gradient for ``qkv`` and / or ``bias`` as ``needs_input_grad`` asks, the bias's in the
+    shape it was given (summed over broadcast axes).  When qkv needs none, the dq / dk / dv
+    work is not launched."""
+    return _AttentionBiasTrainFn.apply(qkv, bias, num_heads, scale, border)
 
 
 class BlockWeights:
