@@ -145,3 +145,12 @@ def fp16_twin(test):
         return test(*args, **kwargs)
     twin.__name__ = twin.__qualname__ = test.__name__ + '_fp16'
     return twin
+
+
+def halo_is_zero(grid):
+    """A PaddedVolume / PaddedImage holds zeros on its halo rows and in its guard rows."""
+    B, C, *spatial = grid.shape
+    full = grid.rows.view(B, *(v + 2 for v in spatial), C).float().clone()
+    full[(slice(None),) + (slice(1, -1),) * len(spatial)] = 0
+    return (float(full.abs().sum()) == 0.0 and float(grid.storage[:grid.guard].abs().sum()) == 0.0
+            and float(grid.storage[grid.guard + grid.M:].abs().sum()) == 0.0)

@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.helpers import flavour, fp16_twin, half_tol, to_half  # noqa: F401
+from tests.helpers import halo_is_zero as _halo_is_zero
 from veon_amd import _lib, conv3d_ops, half
 from veon_amd.models.semantic_net import AlignBody3D, ResBlock3D
 
@@ -149,21 +150,17 @@ def _ncdhw(vol):
     return vol.interior().permute(0, 4, 1, 2, 3).double()
 
 
-def _halo_is_zero(vol):
-    B, C, Z, Y, X = vol.shape
-    grid = vol.rows.view(B, Z + 2, Y + 2, X + 2, C).float().clone()
-    grid[:, 1:-1, 1:-1, 1:-1] = 0
-    return (float(grid.abs().sum()) == 0.0 and float(vol.storage[:vol.guard].abs().sum()) == 0.0
-            and float(vol.storage[vol.guard + vol.M:].abs().sum()) == 0.0)
-
-
 def _within_half_rounding(got, want):
     rms = want.pow(2).mean().sqrt().item()
     tol = half_tol(2.0 ** -8, 2e-3)
     return bool(((got - want).abs() <= want.abs() * tol['rtol'] + tol['atol'] * rms).all())
 
 
-@pytest.mark.parametrize('B,C,Z,Y,X', [(2, 64, 4, 10, 12), (2, 128, 3, 7, 5), (1, 256, 8, 100, 100)])
+# the narrow and wide ones: one lane per row, idle threads, one row in flight (the 'bn' rows
+# of tests/reduce_seams.py)
+@pytest.mark.parametrize('B,C,Z,Y,X', [(2, 64, 4, 10, 12), (2, 128, 3, 7, 5), (1, 256, 8, 100, 100),
+                                       (1, 8, 2, 3, 4), (1, 72, 2, 3, 4), (1, 1032, 1, 2, 3),
+                                       (1, 2048, 1, 1, 2)])
 def test_bn_passes_against_fp64(B, C, Z, Y, X, flavour):
     """Sums, normalise (+ identity, + ReLU) and the backward pass against the fp64 torch
     functions of tests/test_body_train.py on the same half inputs."""

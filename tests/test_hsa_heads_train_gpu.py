@@ -136,16 +136,19 @@ def _within_half_rounding(got, want):
     return bool(((got - want).abs() <= want.abs() * tol['rtol'] + tol['atol'] * rms).all())
 
 
-# 384: 48 lanes of a wave hold the row, not a power of two
-@pytest.mark.parametrize('T,d', [(240, 64), (70, 128), (45, 384), (16896, 384)])
+# 384: 48 lanes of a wave hold the row, not a power of two; 576 and 1024: the
+# two-chunks-per-lane kernel, with 8 and with all 64 lanes holding a second chunk
+@pytest.mark.parametrize('T,d', [(240, 64), (70, 128), (45, 384), (16896, 384), (13, 576),
+                                 (11, 1024)])
 def test_row_passes_against_fp64(T, d, flavour):
     """colsum, gelu, gelu_bwd and layernorm_f32_bwd (dout as fp32 and as half) against the
     fp64 closed forms on the same inputs.  Elementwise half results within half rounding;
     dx (fp32) within 1e-5 of the row's RMS; sums within (T + 8) 2^-24 sum |terms| (T terms,
     and 8 for the fp32-rounded xhat factor of a term; the + 8 did not have to move).
-    Measured on an MI355X: the largest error of any sum is 1.33 x 2^-24 sum |terms| (at
-    (45, 384), bound 53; 0.08 at (16 896, 384), bound 16 904), the largest dx error 1.2e-6 of
-    the row's RMS, the same in both flavours."""
+    Measured on an MI355X: the largest error of any sum is 2.45 x 2^-24 sum |terms| (at
+    (13, 576), bound 21; 2.44 at (11, 1024), bound 19; 1.33 at (45, 384), bound 53; 0.08 at
+    (16 896, 384), bound 16 904), the largest dx error 1.2e-6 of the row's RMS, in both
+    flavours."""
     g = torch.Generator().manual_seed(T + d)
     y = (torch.randn(T, d, generator=g) * 1.5 + 0.3).to(half.dtype()).to(DEV)
     dh = torch.randn(T, d, generator=g).to(half.dtype()).to(DEV)

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void k_rows_colsum(const bf16_t* __restrict__ 
 }
 
 // h = GELU(y), or dy = dh GELU'(y): one 16-byte chunk per thread, fp32 from the stored
-// half value, both from the one erfc evaluation of gelu_and_slope.  QUICK: CLIP's
+// half value, both from gelu_and_slope (one rcp, one exp2).  QUICK: CLIP's
 // QuickGELU y sigma(1.702 y) and its slope sigma + 1.702 y sigma (1 - sigma).
 template <bool BWD, bool QUICK = false>
 __global__ __launch_bounds__(256) void k_gelu(const bf16_t* __restrict__ y,
@@ -82,7 +82,9 @@ __global__ __launch_bounds__(256) void k_gelu(const bf16_t* __restrict__ y,
       const float yv = bf2f((bf16_t)c[k]);
       const float sg = 1.f / (1.f + __expf(-1.702f * yv));
       g = yv * sg;
-      slope = sg + 1.702f * yv * sg * (1.f - sg);
+      // where sigma has saturated the second term is 0; evaluated as written it is
+      // inf * 0 for the largest bf16 arguments (1.702 |y| overflows fp32)
+      slope = sg * (1.f - sg) == 0.f ? sg : sg + 1.702f * yv * sg * (1.f - sg);
     } else {
       gelu_and_slope(bf2f((bf16_t)c[k]), &g, &slope);
     }
