@@ -1110,6 +1110,38 @@ int veon_occ_classify(const float *sem, const int64_t *sem_strides, int Q,
                       int yi, int xi, int Zo, int Yo, int Xo, float *sem_out,
                       float *bin_out, int64_t *cls_out, void *stream);
 
+/* ======== occ_eval.hip ============================================================== */
+
+/* The label-only tail: what VEONTemporal.simple_test returns (detectors/
+ * veon_temporal.py:219-241 keeps only occ_pred_cls, as uint8).  Inputs, strides, extent
+ * checks and the label rule are those of veon_occ_classify (first maximum of the class
+ * logits where they hold no NaN and a finite maximum and softmax(bin)[0] > 0.5, else
+ * Q), computed by the same code: labels (B,Xo,Yo,Zo) uint8 are bit-equal to its cls_out
+ * and are the ONLY output.  1 <= Q <= 254, Zo <= 2048.
+ * Optionally the confusion matrix of Metric_mIoU (mmdet3d/datasets/occ_metrics.py:
+ * 78-147, hist_info after add_batch's masking) in the same pass: gt (B,Xo,Yo,Zo) uint8
+ * and hist (n_cl*n_cl int64, n_cl = Q + 1 <= 64) are given together or both NULL; mask
+ * (B,Xo,Yo,Zo) uint8, 0 = skip, NULL = no mask.  Every voxel with mask != 0 and
+ * gt < n_cl adds 1 to hist[n_cl*gt + label] (gt = 255, "ignore", falls out by the range
+ * test).  hist is ACCUMULATED into, never cleared: the metric's state stays on the device
+ * across samples.  Integer atomics: exact, the same for every run.  Nothing is allocated
+ * or read back. */
+int veon_occ_labels(const float *sem, const int64_t *sem_strides, int Q, const float *bin,
+                    const int64_t *bin_strides, int B, int zi, int yi, int xi, int Zo,
+                    int Yo, int Xo, uint8_t *labels, const uint8_t *gt,
+                    const uint8_t *mask, int64_t *hist, void *stream);
+
+/* The same confusion matrix for labels that exist already (occ_metrics.py:78-147): pred
+ * holds n labels of pred_elem_bytes = 1 (uint8) or 8 (int64, veon_occ_classify's
+ * cls_out) in the order of gt (n uint8) and mask (n uint8, 0 = skip, NULL = no mask);
+ * 1 <= n < 2^31, 1 <= n_cl <= 64.  Every voxel with mask != 0 and gt < n_cl adds 1 to
+ * hist[n_cl*gt + pred] (n_cl*n_cl int64, accumulated into); such a voxel whose
+ * prediction is outside [0, n_cl) counts in no bin and sets *flag (a device int, may be
+ * NULL; never cleared here) to 1. */
+int veon_occ_confusion(const void *pred, int pred_elem_bytes, const uint8_t *gt,
+                       const uint8_t *mask, int64_t n, int n_cl, int64_t *hist, int *flag,
+                       void *stream);
+
 /* ======== occ_retrieval.hip ========================================================= */
 
 /* Open-vocabulary point retrieval, the `retrieval=True` branch of

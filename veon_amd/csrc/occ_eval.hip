@@ -1,0 +1,347 @@
+// On-device Occ3D evaluation (Metric_mIoU, mmdet3d/datasets/occ_metrics.py:78-147):
+// the label-only tail of the occupancy path with the confusion matrix fused in, and the
+// same confusion matrix for label volumes that already exist.
+//
+// k_occ_labels computes what k_occ_classify (occ_head.hip) computes per voxel -- the
+// same source indices, corner offsets, blend nest and class loop (occ_tail.h), so the
+// same label bit for bit -- and writes NOTHING but the uint8 label volume (B,Xo,Yo,Zo)
+// that VEONTemporal.simple_test returns (detectors/veon_temporal.py:219-241): 640 KB
+// at the VEON shape instead of 48 MB of upsampled logits and 5 MB of int64 labels.
+//
+// Mapping.  A block owns tiles of TX x TY (x,y) columns, every z of them.  Lanes walk
+// x fastest, then y, then z -- the order of the low-resolution rows, as in
+// k_occ_classify -- and drop each label as one byte into LDS at its place in the
+// (x, y, z) order of the output.  After a barrier the tile is written out as runs of
+// TY*Zo contiguous bytes per x, W = 16 / 8 / 4 / 1 bytes per lane (the largest that
+// divides Zo and the alignment of the pointers); the ground truth and the mask are
+// read with the same W-byte accesses at the same offsets.
+//
+// Histogram.  n_cl*n_cl 32-bit counters in LDS, zeroed once per block; every voxel
+// with mask != 0 and gt < n_cl adds 1 to counter n_cl*gt + label with an LDS integer
+// atomic (a lane first merges equal neighbours among its W voxels: one z column is
+// mostly one class).  The grid is bounded and strides over the tiles, and after the
+// last tile each block adds its non-zero counters to the global int64 histogram with
+// 64-bit integer atomics.  Integer sums: exact and independent of the order.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "occ_tail.h"
+#include "veon_hip.h"
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int TX = 16;            // x columns of a tile
+constexpr int TILE_VOXELS = 1024; // TY is chosen for about this many voxels per tile
+constexpr int MAX_BLOCKS = 2048;  // grid bound; more work is strided over
+constexpr int MAX_CL = 64;        // 64*64 counters = 16 KB of LDS
+constexpr int MAX_ZO = 2048;      // TX*Zo bytes of staged labels = 32 KB of LDS
+
+template <int W> struct Bytes;
+template <> struct Bytes<1> { using T = uint8_t; };
+template <> struct Bytes<4> { using T = uint32_t; };
+template <> struct Bytes<8> { using T = uint2; };
+template <> struct Bytes<16> { using T = uint4; };
+
+struct Geometry {
+  int zi, yi, xi, Zo, Yo, Xo;
+  float scz, scy, scx;
+};
+
+// The label of output voxel (b, z, y, x): k_occ_classify without its stores.
+template <bool VEC4>
+__device__ __forceinline__ int label_of(const float* __restrict__ sem, const Strides5& ss,
+                                        int Q, const float* __restrict__ bin,
+                                        const Strides5& bs, const Geometry& g, int b, int z,
+                                        int y, int x) {
+  const Axis az = source(z, g.scz, g.zi), ay = source(y, g.scy, g.yi),
+             ax = source(x, g.scx, g.xi);
+  float vmax = -INFINITY;
+  int cls = 0;
+  bool bad = false;
+  const float* sp = sem + b * ss.b;
+  const Corners ks = corners(ss, az, ay, ax);
+  if (VEC4) {
+#pragma unroll 1
+    for (int c = 0; c < Q; c += 4) {
+      float4 k4[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) k4[q] = *reinterpret_cast<const float4*>(sp + c + ks.o[q]);
+      float val4[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        auto at = [&](int q) { return reinterpret_cast<const float*>(&k4[q])[e]; };
+        val4[e] = az.l0 * (ay.l0 * (ax.l0 * at(0) + ax.l1 * at(1)) +
+                           ay.l1 * (ax.l0 * at(2) + ax.l1 * at(3))) +
+                  az.l1 * (ay.l0 * (ax.l0 * at(4) + ax.l1 * at(5)) +
+                           ay.l1 * (ax.l0 * at(6) + ax.l1 * at(7)));
+      }
+      // Every value is needed here, also those of the surplus floats past class Q - 1:
+      // without the stores of k_occ_classify the compiler otherwise computes them under
+      // the branch below, splits each 16-byte load into three and waits for each part.
+#pragma unroll
+      for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(val4[e]));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (c + e < Q) {
+          const float val = val4[e];
+          bad |= val != val;
+          if (val > vmax) {
+            vmax = val;
+            cls = c + e;
+          }
+        }
+      }
+    }
+  } else {
+#pragma unroll 2
+    for (int c = 0; c < Q; ++c) {
+      const float val = blend(sp + c * ss.c, ks, az, ay, ax);
+      bad |= val != val;
+      if (val > vmax) {
+        vmax = val;
+        cls = c;
+      }
+    }
+  }
+  const bool scored = !bad && vmax < INFINITY && vmax > -INFINITY;
+  const float* bp = bin + b * bs.b;
+  const Corners kb = corners(bs, az, ay, ax);
+  const float o0 = blend(bp, kb, az, ay, ax), o1 = blend(bp + bs.c, kb, az, ay, ax);
+  const float om = o0 > o1 ? o0 : o1;
+  const float e0 = expf(o0 - om), e1 = expf(o1 - om);
+  const bool keep = scored && (e0 / (e0 + e1) > 0.5f);
+  return keep ? cls : Q;
+}
+
+__device__ __forceinline__ void zero_counters(unsigned* cnt, int n_cl) {
+  for (int i = threadIdx.x; i < n_cl * n_cl; i += THREADS) cnt[i] = 0u;
+}
+
+// after a barrier: the block's non-zero counters into the global histogram
+__device__ __forceinline__ void flush_counters(const unsigned* cnt, int n_cl,
+                                               unsigned long long* __restrict__ hist) {
+  for (int i = threadIdx.x; i < n_cl * n_cl; i += THREADS) {
+    const unsigned c = cnt[i];
+    if (c) atomicAdd(hist + i, (unsigned long long)c);
+  }
+}
+
+template <bool VEC4, int W>
+__global__ __launch_bounds__(THREADS) void k_occ_labels(
+    const float* __restrict__ sem, Strides5 ss, int Q, const float* __restrict__ bin,
+    Strides5 bs, int B, Geometry g, int TY, uint8_t* __restrict__ labels,
+    const uint8_t* __restrict__ gt, const uint8_t* __restrict__ mask,
+    unsigned long long* __restrict__ hist) {
+  using T = typename Bytes<W>::T;
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int Zo = g.Zo, Yo = g.Yo, Xo = g.Xo;
+  const int col = TY * Zo;   // staged bytes of one x of the tile, (y, z) order
+  uint8_t* stage = smem;
+  unsigned* cnt = reinterpret_cast<unsigned*>(smem + ((TX * col + 15) & ~15));
+  const int n_cl = Q + 1;
+  if (hist) zero_counters(cnt, n_cl);   // (the first barrier below orders it)
+
+  const int tiles_x = (Xo + TX - 1) / TX, tiles_y = (Yo + TY - 1) / TY;
+  const int tiles = B * tiles_y * tiles_x;   // <= B*Yo*Xo < 2^31
+  for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
+    const int x0 = tx * TX, y0 = ty * TY;
+    const int nx = Xo - x0 < TX ? Xo - x0 : TX, ny = Yo - y0 < TY ? Yo - y0 : TY;
+
+    for (int i = threadIdx.x; i < TX * col; i += THREADS) {
+      const int xl = i % TX, r = i / TX;
+      const int yl = r % TY, z = r / TY;
+      if (xl < nx && yl < ny)
+        stage[xl * col + yl * Zo + z] =
+            (uint8_t)label_of<VEC4>(sem, ss, Q, bin, bs, g, b, z, y0 + yl, x0 + xl);
+    }
+    __syncthreads();
+
+    // ny*Zo contiguous bytes per x, in LDS and in the output; Zo % W == 0
+    const int units = ny * Zo / W;
+    for (int u = threadIdx.x; u < nx * units; u += THREADS) {
+      const int xl = u / units, k = u - xl * units;
+      const int64_t off = (((int64_t)b * Xo + x0 + xl) * Yo + y0) * Zo + (int64_t)k * W;
+      const T lab = *reinterpret_cast<const T*>(stage + xl * col + k * W);
+      *reinterpret_cast<T*>(labels + off) = lab;
+      if (hist) {
+        const T gv = *reinterpret_cast<const T*>(gt + off);
+        T mv = gv;   // any value: unread without a mask
+        if (mask) mv = *reinterpret_cast<const T*>(mask + off);
+        const uint8_t* lb = reinterpret_cast<const uint8_t*>(&lab);
+        const uint8_t* gb = reinterpret_cast<const uint8_t*>(&gv);
+        const uint8_t* mb = reinterpret_cast<const uint8_t*>(&mv);
+        int run_bin = 0;
+        unsigned run = 0u;
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          if ((!mask || mb[j]) && gb[j] < n_cl) {
+            const int bin_j = gb[j] * n_cl + lb[j];   // label <= Q < n_cl
+            if (run && bin_j != run_bin) {
+              atomicAdd(cnt + run_bin, run);
+              run = 0u;
+            }
+            run_bin = bin_j;
+            ++run;
+          }
+        }
+        if (run) atomicAdd(cnt + run_bin, run);
+      }
+    }
+    __syncthreads();   // the stage is free again; after the last tile: counters complete
+  }
+  if (hist) flush_counters(cnt, n_cl, hist);
+}
+
+__device__ __forceinline__ bool count_one(unsigned* cnt, int n_cl, int64_t p, unsigned gv,
+                                          unsigned mv) {
+  if (!mv || gv >= (unsigned)n_cl) return false;
+  if ((uint64_t)p >= (uint64_t)n_cl) return true;   // in no bin
+  atomicAdd(cnt + gv * n_cl + (int)p, 1u);
+  return false;
+}
+
+// P: the label type (uint8_t or int64_t); E voxels per lane and step (4: gt and mask,
+// and uint8 labels, as one 4-byte load each)
+template <typename P, int E>
+__global__ __launch_bounds__(THREADS) void k_confusion(
+    const P* __restrict__ pred, const uint8_t* __restrict__ gt,
+    const uint8_t* __restrict__ mask, int64_t n, int n_cl,
+    unsigned long long* __restrict__ hist, int* __restrict__ flag) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  unsigned* cnt = reinterpret_cast<unsigned*>(smem);
+  zero_counters(cnt, n_cl);
+  __syncthreads();
+  bool bad = false;
+  const int64_t groups = (n + E - 1) / E;
+  for (int64_t grp = (int64_t)blockIdx.x * THREADS + threadIdx.x; grp < groups;
+       grp += (int64_t)gridDim.x * THREADS) {
+    const int64_t base = grp * E;
+    if (E == 4 && base + 4 <= n) {
+      const uint32_t gv = *reinterpret_cast<const uint32_t*>(gt + base);
+      const uint32_t mv = mask ? *reinterpret_cast<const uint32_t*>(mask + base) : ~0u;
+      int64_t p[4];
+      if (sizeof(P) == 1) {
+        const uint32_t pv = *reinterpret_cast<const uint32_t*>(pred + base);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = (pv >> (8 * j)) & 0xffu;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = (int64_t)pred[base + j];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        bad |= count_one(cnt, n_cl, p[j], (gv >> (8 * j)) & 0xffu, (mv >> (8 * j)) & 0xffu);
+    } else {
+      const int64_t end = base + E < n ? base + E : n;
+      for (int64_t i = base; i < end; ++i)
+        bad |= count_one(cnt, n_cl, (int64_t)pred[i], gt[i], mask ? mask[i] : 1u);
+    }
+  }
+  if (bad && flag) *flag = 1;
+  __syncthreads();
+  flush_counters(cnt, n_cl, hist);
+}
+
+inline int launch_status() {
+  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
+}
+
+inline bool aligned(const void* p, int w) {
+  return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(w - 1)) == 0;
+}
+
+template <bool VEC4>
+void launch_labels(int W, int blocks, size_t lds, hipStream_t st, const float* sem,
+                   const Strides5& ss, int Q, const float* bin, const Strides5& bs, int B,
+                   const Geometry& g, int TY, uint8_t* labels, const uint8_t* gt,
+                   const uint8_t* mask, unsigned long long* hist) {
+#define VEON_LABELS(w)                                                                   \
+  hipLaunchKernelGGL((k_occ_labels<VEC4, w>), dim3((unsigned)blocks), dim3(THREADS), lds, \
+                     st, sem, ss, Q, bin, bs, B, g, TY, labels, gt, mask, hist)
+  switch (W) {
+    case 16: VEON_LABELS(16); break;
+    case 8: VEON_LABELS(8); break;
+    case 4: VEON_LABELS(4); break;
+    default: VEON_LABELS(1); break;
+  }
+#undef VEON_LABELS
+}
+
+}  // namespace
+
+extern "C" int veon_occ_labels(const float* sem, const int64_t* sem_strides, int Q,
+                               const float* bin, const int64_t* bin_strides, int B, int zi,
+                               int yi, int xi, int Zo, int Yo, int Xo, uint8_t* labels,
+                               const uint8_t* gt, const uint8_t* mask, int64_t* hist,
+                               void* stream) {
+  if (!sem || !bin || !sem_strides || !bin_strides || !labels || Q <= 0 || Q > 254 ||
+      B <= 0 || zi <= 0 || yi <= 0 || xi <= 0 || Zo <= 0 || Yo <= 0 || Xo <= 0 ||
+      Zo > MAX_ZO)
+    return VEON_ERR_BAD_ARG;
+  // the histogram needs the ground truth and the other way round; a mask needs both
+  if ((gt != nullptr) != (hist != nullptr) || (mask && !gt)) return VEON_ERR_BAD_ARG;
+  if (hist && Q + 1 > MAX_CL) return VEON_ERR_BAD_ARG;
+  const int64_t total = (int64_t)B * Zo * Yo * Xo;
+  if (total > 0x7fffffffLL) return VEON_ERR_BAD_ARG;
+  if (!strides_fit(sem_strides, zi, yi, xi) || !strides_fit(bin_strides, zi, yi, xi))
+    return VEON_ERR_BAD_ARG;
+  const Strides5 ss{sem_strides[0], sem_strides[1], sem_strides[2], sem_strides[3],
+                    sem_strides[4]};
+  const Strides5 bs{bin_strides[0], bin_strides[1], bin_strides[2], bin_strides[3],
+                    bin_strides[4]};
+  // ATen: scale = in / out in float (area_pixel_compute_scale, no scale_factor given)
+  const Geometry g{zi, yi, xi, Zo, Yo, Xo, (float)zi / (float)Zo, (float)yi / (float)Yo,
+                   (float)xi / (float)Xo};
+  // about four voxels per thread and tile (16 x 4 columns of 16 at the VEON shape, 650
+  // tiles): measured against one, two and eight, it is the fastest with and without the
+  // histogram -- fewer barriers and fewer blocks that flush counters, still every SIMD busy
+  int TY = TILE_VOXELS / (TX * Zo);
+  TY = TY < 1 ? 1 : (TY > Yo ? Yo : TY);
+  int W = 1;
+  for (int w : {16, 8, 4}) {
+    if (Zo % w == 0 && aligned(labels, w) && aligned(gt, w) && aligned(mask, w)) {
+      W = w;
+      break;
+    }
+  }
+  const int64_t tiles = (int64_t)B * ((Yo + TY - 1) / TY) * ((Xo + TX - 1) / TX);
+  const int64_t rounds = (tiles + MAX_BLOCKS - 1) / MAX_BLOCKS;
+  const int blocks = (int)((tiles + rounds - 1) / rounds);   // even shares, <= MAX_BLOCKS
+  const size_t lds = (size_t)((TX * TY * Zo + 15) & ~15) +
+                     (hist ? sizeof(unsigned) * (Q + 1) * (Q + 1) : 0);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
+  if (vec4_rows(sem, ss, Q))
+    launch_labels<true>(W, blocks, lds, st, sem, ss, Q, bin, bs, B, g, TY, labels, gt, mask, h);
+  else
+    launch_labels<false>(W, blocks, lds, st, sem, ss, Q, bin, bs, B, g, TY, labels, gt, mask, h);
+  return launch_status();
+}
+
+extern "C" int veon_occ_confusion(const void* pred, int pred_elem_bytes, const uint8_t* gt,
+                                  const uint8_t* mask, int64_t n, int n_cl, int64_t* hist,
+                                  int* flag, void* stream) {
+  if (!pred || !gt || !hist || (pred_elem_bytes != 1 && pred_elem_bytes != 8) || n <= 0 ||
+      n > 0x7fffffffLL || n_cl <= 0 || n_cl > MAX_CL || !aligned(pred, pred_elem_bytes))
+    return VEON_ERR_BAD_ARG;
+  const bool quads = aligned(gt, 4) && aligned(mask, 4) &&
+                     (pred_elem_bytes == 8 || aligned(pred, 4));
+  const int64_t groups = quads ? (n + 3) / 4 : n;
+  int64_t blocks = (groups + THREADS - 1) / THREADS;
+  blocks = blocks > MAX_BLOCKS ? MAX_BLOCKS : blocks;
+  const size_t lds = sizeof(unsigned) * n_cl * n_cl;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
+#define VEON_CONFUSION(P, E)                                                              \
+  hipLaunchKernelGGL((k_confusion<P, E>), dim3((unsigned)blocks), dim3(THREADS), lds, st, \
+                     static_cast<const P*>(pred), gt, mask, n, n_cl, h, flag)
+  if (pred_elem_bytes == 1) {
+    if (quads) VEON_CONFUSION(uint8_t, 4); else VEON_CONFUSION(uint8_t, 1);
+  } else {
+    if (quads) VEON_CONFUSION(int64_t, 4); else VEON_CONFUSION(int64_t, 1);
+  }
+#undef VEON_CONFUSION
+  return launch_status();
+}

@@ -19,52 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "occ_tail.h"
 #include "veon_hip.h"
 
 namespace {
-
-struct Strides5 {
-  int64_t b, c, z, y, x;
-};
-
-struct Axis {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ Axis source(int dst, float scale, int in_size) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  Axis a;
-  a.i0 = (int)src;
-  a.i1 = a.i0 + (a.i0 < in_size - 1 ? 1 : 0);
-  a.l1 = src - (float)a.i0;
-  a.l0 = 1.f - a.l1;
-  return a;
-}
-
-// the eight corner offsets (elements, within one batch element and channel) of a
-// voxel; 32-bit: the host checks the extent
-struct Corners {
-  int o[8];
-};
-
-__device__ __forceinline__ Corners corners(const Strides5& s, const Axis& az,
-                                           const Axis& ay, const Axis& ax) {
-  const int z0 = az.i0 * (int)s.z, z1 = az.i1 * (int)s.z;
-  const int y0 = ay.i0 * (int)s.y, y1 = ay.i1 * (int)s.y;
-  const int x0 = ax.i0 * (int)s.x, x1 = ax.i1 * (int)s.x;
-  return Corners{{z0 + y0 + x0, z0 + y0 + x1, z0 + y1 + x0, z0 + y1 + x1,
-                  z1 + y0 + x0, z1 + y0 + x1, z1 + y1 + x0, z1 + y1 + x1}};
-}
-
-__device__ __forceinline__ float blend(const float* __restrict__ p, const Corners& k,
-                                       const Axis& az, const Axis& ay, const Axis& ax) {
-  return az.l0 * (ay.l0 * (ax.l0 * p[k.o[0]] + ax.l1 * p[k.o[1]]) +
-                  ay.l1 * (ax.l0 * p[k.o[2]] + ax.l1 * p[k.o[3]])) +
-         az.l1 * (ay.l0 * (ax.l0 * p[k.o[4]] + ax.l1 * p[k.o[5]]) +
-                  ay.l1 * (ax.l0 * p[k.o[6]] + ax.l1 * p[k.o[7]]));
-}
 
 // VEC4: the class logits are channels-last (channel stride 1, rows 16-byte aligned,
 // at least 4*ceil(Q/4) floats per row): four classes per 16-byte corner load -- the
@@ -169,11 +127,8 @@ extern "C" int veon_occ_classify(const float* sem, const int64_t* sem_strides, i
   const int64_t total = (int64_t)B * Zo * Yo * Xo;
   const int64_t blocks = (total + 255) / 256;
   if (total > 0x7fffffffLL) return VEON_ERR_BAD_ARG;
-  for (const int64_t* st : {sem_strides, bin_strides}) {  // 32-bit corner offsets
-    if (st[2] < 0 || st[3] < 0 || st[4] < 0 ||
-        st[2] * (zi - 1) + st[3] * (yi - 1) + st[4] * (xi - 1) > 0x7fffffffLL)
-      return VEON_ERR_BAD_ARG;
-  }
+  if (!strides_fit(sem_strides, zi, yi, xi) || !strides_fit(bin_strides, zi, yi, xi))
+    return VEON_ERR_BAD_ARG;
   const Strides5 ss{sem_strides[0], sem_strides[1], sem_strides[2], sem_strides[3],
                     sem_strides[4]};
   const Strides5 bs{bin_strides[0], bin_strides[1], bin_strides[2], bin_strides[3],
@@ -181,11 +136,7 @@ extern "C" int veon_occ_classify(const float* sem, const int64_t* sem_strides, i
   // ATen: scale = in / out in float (area_pixel_compute_scale, no scale_factor given)
   const float scz = (float)zi / (float)Zo, scy = (float)yi / (float)Yo,
               scx = (float)xi / (float)Xo;
-  const int q4 = (Q + 3) / 4 * 4;
-  const bool vec4 = ss.c == 1 && (reinterpret_cast<uintptr_t>(sem) & 15u) == 0 &&
-                    ss.b % 4 == 0 && ss.z % 4 == 0 && ss.y % 4 == 0 && ss.x % 4 == 0 &&
-                    ss.x >= q4;
-  if (vec4)
+  if (vec4_rows(sem, ss, Q))
     hipLaunchKernelGGL(k_occ_classify<true>, dim3((unsigned)blocks), dim3(256), 0,
                        static_cast<hipStream_t>(stream), sem, ss, Q, bin, bs, B, zi, yi,
                        xi, Zo, Yo, Xo, scz, scy, scx, sem_out, bin_out, cls_out);

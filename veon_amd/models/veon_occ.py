@@ -261,7 +261,8 @@ class VeonOccupancyPath(nn.Module):
         vt = self.view_transformer
         return align_after_lss(volume, adj_metas, vt.grid_config, tuple(vt.ds))
 
-    def _tail(self, x, prev_volumes=None, return_features=False):
+    def _tail(self, x, prev_volumes=None, return_features=False, labels_only=False,
+              count=None):
         """Conv3d body -> heads -> classifier -> upsampling -> arg-max on a lifted
         PaddedVolume (san_in_veon_temporal.py:196-211, veon_temporal.py:219-227)."""
         dec = self.occ_decoder
@@ -270,13 +271,29 @@ class VeonOccupancyPath(nn.Module):
         x = dec.__dict__['_body'](x, return_volume=True)
         bin_occ = dec.occupancy_pred(x)
         feat = dec.feat_pred(x, return_volume=True)
-        return self._classify(bin_occ, feat, return_features)
+        return self._classify(bin_occ, feat, return_features, labels_only, count)
 
-    def _classify(self, bin_occ, feat, return_features=False):
-        from .. import conv3d_ops
+    def _classify(self, bin_occ, feat, return_features=False, labels_only=False,
+                  count=None):
+        """``labels_only``: the output holds ``occ_pred_cls`` as uint8 (what
+        ``VEONTemporal.simple_test`` returns, veon_temporal.py:219-241) and neither
+        ``sem_occ`` nor ``bin_occ``; the upsampled volumes are then not written at all on
+        the native path.  ``count`` (with ``labels_only``): (gt, mask or None, hist) of
+        ``occ_eval.occ_labels`` -- the labels' confusion matrix is added to ``hist``."""
+        from .. import conv3d_ops, occ_eval
         W = self.ov_classifier_weight
         extra = {'feat_low': feat, 'bin_low': bin_occ} if return_features else {}
-        if bin_occ.is_cuda and not torch.is_grad_enabled() and bin_occ.shape[1] == 2:
+        if count is not None and not labels_only:
+            raise ValueError('count needs labels_only=True')
+        native = bin_occ.is_cuda and not torch.is_grad_enabled() and bin_occ.shape[1] == 2
+        if native and labels_only:
+            # the same labels, and nothing but the labels, from one kernel
+            low = classifier_logits_low(W, feat)
+            gt, mask, hist = count or (None, None, None)
+            occ = occ_eval.occ_labels(low.float(), bin_occ.float(), self.occ_size, gt,
+                                      mask, hist)
+            return {'occ_pred_cls': occ, **extra}
+        if native:
             # upsampling x2, both softmaxes, arg-max and the label volume: one kernel
             low = classifier_logits_low(W, feat)
             sem_occ, bin_up, occ = conv3d_ops.occ_classify(low.float(), bin_occ.float(),
@@ -289,8 +306,14 @@ class VeonOccupancyPath(nn.Module):
         score, cls = torch.softmax(sem_occ, dim=1).max(dim=1)
         keep = (score > 0.0) & (torch.softmax(bin_occ, dim=1)[:, 0] > 0.5)
         occ = torch.where(keep, cls, torch.full_like(cls, sem_occ.shape[1]))
-        return {'bin_occ': bin_occ, 'sem_occ': sem_occ,
-                'occ_pred_cls': occ.permute(0, 3, 2, 1).contiguous(), **extra}
+        occ = occ.permute(0, 3, 2, 1).contiguous()
+        if labels_only:
+            occ = occ.to(torch.uint8)
+            if count is not None:
+                gt, mask, hist = count
+                occ_eval.confusion(occ, gt, mask, hist.shape[0], hist)
+            return {'occ_pred_cls': occ, **extra}
+        return {'bin_occ': bin_occ, 'sem_occ': sem_occ, 'occ_pred_cls': occ, **extra}
 
     def lift_cameras(self, images, img_metas, lo, hi, depth=None):
         """The UN-POOLED lifted volume (B, C, Z, Y, X) fp32 of cameras [lo, hi) of
@@ -403,25 +426,26 @@ class VeonOccupancyPath(nn.Module):
             return out
         return vol.view(b, c, z // dz, dz, y // dy, dy, x // dx, dx).amax(dim=(3, 5, 7))
 
-    def from_volume(self, vol, return_features=False):
+    def from_volume(self, vol, return_features=False, labels_only=False):
         """Everything after the (reduced) un-pooled lifted volume (B, C, Z, Y, X):
         ds_feat max-pool, Conv3d body, heads, classifier, arg-max."""
-        return self.from_pooled(self._max_pool(vol), return_features)
+        return self.from_pooled(self._max_pool(vol), return_features, labels_only)
 
-    def from_pooled(self, pooled, return_features=False):
+    def from_pooled(self, pooled, return_features=False, labels_only=False):
         """Conv3d body, heads, classifier, arg-max on the pooled volume
-        (B, C, Z/dz, Y/dy, X/dx)."""
+        (B, C, Z/dz, Y/dy, X/dx); ``labels_only``: see ``forward``."""
         from .. import conv3d_ops
         b, c = pooled.shape[:2]
         dec = self.occ_decoder
         if pooled.is_cuda and dec._fast_path(pooled[:, :1, 0]):
             lifted = dec._lift_volume(b, c, pooled.device)
             return self._tail(conv3d_ops.pack(pooled, out=lifted),
-                              return_features=return_features)
+                              return_features=return_features, labels_only=labels_only)
         xx = pooled
         for layer_3d in dec.layers_3d_body:
             xx = layer_3d(xx)
-        return self._classify(dec.occupancy_pred(xx), dec.feat_pred(xx), return_features)
+        return self._classify(dec.occupancy_pred(xx), dec.feat_pred(xx), return_features,
+                              labels_only)
 
     def retrieve(self, out, points_indices, embeddings, batch=0):
         """Open-vocabulary point retrieval (the reference's ``retrieval=True`` branch,
@@ -475,7 +499,7 @@ class VeonOccupancyPath(nn.Module):
         return {'feat_low': out['feat_occ'], 'bin_low': out['bin_occ']}
 
     def forward(self, images, img_metas, prev_volumes=None, depth=None, with_2d=False,
-                return_features=False):
+                return_features=False, labels_only=False):
         """images (B, N, 3, H, W); img_metas = (sensor2egos, ego2globals, intrins,
         post_rots, post_trans, bda) as the reference's ``img[1:7]``;
         ``prev_volumes``: aligned lifted volumes of the past frames, newest first
@@ -486,7 +510,45 @@ class VeonOccupancyPath(nn.Module):
         back under ``2d_*`` keys.  ``return_features``: also ``feat_low`` (the sem head's
         low-resolution feature volume: its PaddedVolume on the native path -- a buffer
         the module reuses, valid until its next forward -- else (B, C, z, y, x)) and
-        ``bin_low`` (B, 2, z, y, x), the inputs of ``retrieve``."""
+        ``bin_low`` (B, 2, z, y, x), the inputs of ``retrieve``.  ``labels_only``: only
+        ``occ_pred_cls``, as uint8 (B, X, Y, Z) -- all that ``VEONTemporal.simple_test``
+        returns (veon_temporal.py:219-241) -- without ``sem_occ`` / ``bin_occ``; on the
+        native path the upsampled logits are then never written (that kernel takes grids
+        of at most 2048 cells in z and at most 254 classes, and raises beyond)."""
+        return self._run(images, img_metas, prev_volumes, depth, with_2d, return_features,
+                         labels_only)
+
+    def evaluate(self, images, img_metas, voxel_semantics, mask_camera, metric,
+                 prev_volumes=None, depth=None):
+        """One evaluation step of the reference's ``dataset.evaluate`` loop
+        (``Metric_mIoU.add_batch``, mmdet3d/datasets/occ_metrics.py:121-135) on the
+        device: the label-only forward under ``no_grad``, with the confusion matrix of
+        the B samples against ``voxel_semantics`` (B, X, Y, Z) added to ``metric.hist``
+        (an ``occ_eval.OccMiouMetric`` on the images' device) by the tail kernel
+        itself; ``mask_camera`` (B, X, Y, Z) is applied when the metric uses the image
+        mask.  Nothing is read back.  -> the uint8 labels (B, X, Y, Z)."""
+        n_cl = self.ov_classifier_weight.shape[0] + 1
+        if metric.num_classes != n_cl:
+            raise ValueError('the metric counts %d classes, the path predicts %d (+ free)'
+                             % (metric.num_classes, n_cl - 1))
+        if metric.hist.device != images.device:
+            raise ValueError('the metric lives on %s, the images on %s'
+                             % (metric.hist.device, images.device))
+        if metric.use_lidar_mask and not metric.use_image_mask:
+            raise ValueError('evaluate() takes the camera mask only')
+        mask = metric.select_mask(None, mask_camera)
+        if metric.use_image_mask and mask is None:
+            raise ValueError('the metric applies the camera mask but none was given')
+        count = (metric.labels_u8(voxel_semantics),
+                 None if mask is None else metric.mask_u8(mask), metric.hist)
+        with torch.no_grad():
+            out = self._run(images, img_metas, prev_volumes, depth, False, False, True,
+                            count)
+        metric.cnt += images.shape[0]
+        return out['occ_pred_cls']
+
+    def _run(self, images, img_metas, prev_volumes, depth, with_2d, return_features,
+             labels_only, count=None):
         if with_2d and self.side_adapter_network is None:
             raise RuntimeError('VeonOccupancyPath was built without side_adapter=True')
         B, N = images.shape[:2]
@@ -503,11 +565,12 @@ class VeonOccupancyPath(nn.Module):
                                    images.device)
             x = dec.fuse(0, None, feats, [supp], depth2, metas2, None, (hf, wf),
                          out_volume=vol, fused=fused)
-            out = self._tail(x, prev_volumes, return_features)
+            out = self._tail(x, prev_volumes, return_features, labels_only, count)
             return self._add_2d(out, images, feats) if with_2d else out
         feats, supp, depth = self._branches(images, depth)
         out = dec(sem_embed_ds, feats, [supp], depth, metas, prev_volumes)
-        out = self._classify(out['bin_occ'], out['feat_occ'], return_features)
+        out = self._classify(out['bin_occ'], out['feat_occ'], return_features,
+                             labels_only, count)
         return self._add_2d(out, images, feats) if with_2d else out
 
     def _add_2d(self, out, images, feats):
