@@ -19,7 +19,7 @@
  * The ctypes binding (veon_amd/_lib.py) reads its argument types from THIS file, so
  * every declaration below keeps to one style: C89 prototypes `ret veon_name(args);`
  * (they may span lines) with ret in {int, int64_t, void, const char *} and parameters
- * int / int64_t / float / unsigned or a pointer (any pointer is passed as an address);
+ * int / int64_t / float / double / unsigned or a pointer (any pointer is passed as an address);
  * `(void)` for no parameters; comments are C block comments; the only other statement
  * is the one `typedef struct`.  Anything else makes the binding raise at import.
  * Prototypes are grouped by the source file under veon_amd/csrc/ that defines them;
@@ -869,6 +869,43 @@ int veon_bn3d_bwd_apply_bf16(const void *da_padded, const void *a_padded,
                              const void *y_padded, const float *ca, const float *cb,
                              const float *cc, void *dy_padded, void *dz_padded, int B,
                              int C, int Z, int Y, int X, void *stream);
+
+/*
+ * Synchronised train-mode BatchNorm3d (nn.SyncBatchNorm): the statistics interval as a
+ * message.  Stage one of the sums is that of veon_bn3d_sums_bf16 / veon_bn3d_bwd_sums_bf16
+ * (same plan, same workspace); stage two adds the fp32 partials in fp64, many workgroups,
+ * a fixed assignment of partials to lanes and a fixed-order combine: no atomics, no memset,
+ * bit-reproducible whatever `workspace` and `stats` held.
+ *   stats[2C + 1] (fp64): the two sums of the plain entry point, then the LOCAL count
+ *   n = B Z Y X.  Ranks add their buffers elementwise (one all-reduce); the coefficient
+ *   calls below read the total count from the buffer on the device.
+ *   veon_bn3d_bwd_sums_stats_bf16 also writes the local sums rounded to fp32 to
+ *   sums[2][C] (dbeta, dgamma: they stay per rank).
+ * veon_bn_train_coeffs, one launch: mean = s0 / n, var = max(s1 / n - mean^2, 0),
+ * rstd = (var + eps)^-1/2, scale = gamma rstd, shift = beta - mean scale (fp64, stored
+ * fp32).  With running buffers (all three or none): num_batches_tracked += 1, then
+ * running = (1 - f) running + f value with f = momentum, or 1 / num_batches_tracked when
+ * momentum < 0 (nn.BatchNorm's momentum=None); the values are mean (+ mean_offset[c] when
+ * given: a conv bias that was not added to y) and var n / (n - 1).
+ * veon_bn_bwd_coeffs, one launch: ca = gamma rstd, cb = -gamma rstd^2 s1 / n,
+ * cc = -gamma rstd s0 / n - cb mean, the vectors of veon_bn3d_bwd_apply_bf16.
+ * C % 8 == 0, C <= 2048; stats 8-byte aligned.
+ */
+int veon_bn3d_sums_stats_bf16(const void *y_padded, double *stats, void *workspace, int B,
+                              int C, int Z, int Y, int X, void *stream);
+int veon_bn3d_bwd_sums_stats_bf16(const void *da_padded, const void *a_padded,
+                                  const void *y_padded, const float *mean,
+                                  const float *rstd, double *stats, float *sums,
+                                  void *workspace, int B, int C, int Z, int Y, int X,
+                                  void *stream);
+int veon_bn_train_coeffs(const double *stats, const float *gamma, const float *beta,
+                         const float *mean_offset, double eps, double momentum,
+                         float *running_mean, float *running_var,
+                         int64_t *num_batches_tracked, float *mean, float *rstd,
+                         float *scale, float *shift, int C, void *stream);
+int veon_bn_bwd_coeffs(const double *stats, const float *gamma, const float *mean,
+                       const float *rstd, float *ca, float *cb, float *cc, int C,
+                       void *stream);
 
 /* ======== conv2d_train.hip ========================================================== */
 

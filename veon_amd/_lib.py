@@ -50,7 +50,7 @@ class VeonHipError(RuntimeError):
 
 
 _C_TYPES = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
-            'unsigned': ctypes.c_uint}
+            'double': ctypes.c_double, 'unsigned': ctypes.c_uint}
 
 
 def _ctype(decl, is_return=False):

@@ -36,6 +36,11 @@
 // The contraction is split over K; every split writes its fp32 partial tile to a slab
 // of the caller's workspace with plain stores, and a second kernel adds the slabs in
 // index order: no atomics, bit-reproducible.
+//
+// Synchronised BN (nn.SyncBatchNorm, veon_amd/sync_bn.py): the same stage one of the sums,
+// then an fp64 stage two that writes ONE message stats[2C + 1] (two sums and the local
+// count) for the ranks to add, and one coefficient kernel per direction that reads the
+// reduced message: k_bn_sums_stats, k_bn_train_coeffs, k_bn_bwd_coeffs below.
 #include "mfma_common.h"
 #include "wgrad_kernel.h"
 
@@ -202,12 +207,104 @@ bool bn_shape_ok(int B, int C, int Z, int Y, int X) {
          (int64_t)B * (Z + 2) * (Y + 2) * (X + 2) <= 0x3fffffffLL;
 }
 
-int bn_sums_impl(bool bwd, const void* y, const void* da, const void* a, const float* mean,
-                 const float* rstd, float* sums, void* workspace, int B, int C, int Z,
-                 int Y, int X, void* stream) {
-  if (!bn_shape_ok(B, C, Z, Y, X) || !y || !sums || !workspace || !al16(y) ||
-      (bwd && (!da || !a || !mean || !rstd || !al16(da) || !al16(a))))
-    return VEON_ERR_BAD_ARG;
+// ------------------------------------------------- synchronised BN: statistics as a message
+// Stage two of the SyncBatchNorm path: stats[o] = sum over the nblocks partials of output
+// o (of n2 = 2C, a multiple of 16) in fp64.  A workgroup owns 16 consecutive outputs:
+// thread t reads output 16 blockIdx + (t & 15) of the partials (t >> 4) + 0, 16, 32, ...
+// (a wave reads four 64-byte runs of consecutive channels per step) and adds them in
+// that order; thread (t & 15) then adds the 16 slices through LDS in slice order.  Every
+// partial read was written by stage one and every output is stored: nothing depends on
+// what the buffers held.  sums32 (optional): the same sums rounded to fp32; stats[n2]: the
+// local count.
+constexpr int kStatCols = 16, kStatSlices = 16;
+
+__global__ __launch_bounds__(256) void k_bn_sums_stats(const float* __restrict__ part,
+                                                       double* __restrict__ stats,
+                                                       float* __restrict__ sums32, int n2,
+                                                       int nblocks, double count) {
+  __shared__ double red[kStatSlices][kStatCols];
+  const int col = threadIdx.x % kStatCols, sl = threadIdx.x / kStatCols;
+  const int o = blockIdx.x * kStatCols + col;
+  double s = 0.0;
+  for (int b = sl; b < nblocks; b += kStatSlices) s += (double)part[(int64_t)b * n2 + o];
+  red[sl][col] = s;
+  __syncthreads();
+  if (sl == 0) {
+    double t = red[0][col];
+#pragma unroll
+    for (int j = 1; j < kStatSlices; ++j) t += red[j][col];
+    stats[o] = t;
+    if (sums32 != nullptr) sums32[o] = (float)t;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) stats[n2] = count;
+}
+
+// The C-sized algebra between the sums and the apply pass, one workgroup.  n is the TOTAL
+// count (the last element of the reduced buffer).  Every thread reads num_batches_tracked
+// before thread 0 stores its increment (one workgroup: the barrier orders them).
+__global__ __launch_bounds__(256) void k_bn_train_coeffs(
+    const double* __restrict__ stats, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ mean_offset, double eps,
+    double momentum, float* __restrict__ running_mean, float* __restrict__ running_var,
+    int64_t* __restrict__ num_batches_tracked, float* __restrict__ mean,
+    float* __restrict__ rstd, float* __restrict__ scale, float* __restrict__ shift, int C) {
+  const double n = stats[2 * C];
+  double f = momentum;
+  if (running_mean != nullptr) {
+    const int64_t t = *num_batches_tracked + 1;
+    if (momentum < 0.0) f = 1.0 / (double)t;
+    __syncthreads();
+    if (threadIdx.x == 0) *num_batches_tracked = t;
+  }
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const double m = stats[c] / n;
+    double var = stats[C + c] / n - m * m;
+    var = var > 0.0 ? var : 0.0;
+    const double r = 1.0 / sqrt(var + eps);
+    const double sc = (double)gamma[c] * r;
+    mean[c] = (float)m;
+    rstd[c] = (float)r;
+    scale[c] = (float)sc;
+    shift[c] = (float)((double)beta[c] - m * sc);
+    if (running_mean != nullptr) {
+      const double mo = mean_offset != nullptr ? m + (double)mean_offset[c] : m;
+      const double unbiased = var * (n / (n > 1.0 ? n - 1.0 : 1.0));
+      running_mean[c] = (float)((1.0 - f) * (double)running_mean[c] + f * mo);
+      running_var[c] = (float)((1.0 - f) * (double)running_var[c] + f * unbiased);
+    }
+  }
+}
+
+// (ca, cb, cc) of k_bn_bwd_apply from the reduced backward sums and the total count
+__global__ __launch_bounds__(256) void k_bn_bwd_coeffs(
+    const double* __restrict__ stats, const float* __restrict__ gamma,
+    const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ ca,
+    float* __restrict__ cb, float* __restrict__ cc, int C) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const double n = stats[2 * C];
+  const double g = gamma[c], mu = mean[c], r = rstd[c];
+  const double b = -g * r * r * stats[C + c] / n;
+  ca[c] = (float)(g * r);
+  cb[c] = (float)b;
+  cc[c] = (float)(-g * r * stats[c] / n - b * mu);
+}
+
+inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+bool bn_channels_ok(int C) { return C > 0 && C % 8 == 0 && C <= 2048; }
+
+bool bn_sums_args_ok(bool bwd, const void* y, const void* da, const void* a,
+                     const float* mean, const float* rstd, const void* workspace, int B,
+                     int C, int Z, int Y, int X) {
+  return bn_shape_ok(B, C, Z, Y, X) && y && workspace && al16(y) &&
+         (!bwd || (da && a && mean && rstd && al16(da) && al16(a)));
+}
+
+// Stage one of both directions into `workspace`; -> the number of partials
+int bn_sums_stage_one(bool bwd, const void* y, const void* da, const void* a,
+                      const float* mean, const float* rstd, void* workspace, int B, int C,
+                      int Z, int Y, int X, void* stream) {
   const int64_t M = (int64_t)B * (Z + 2) * (Y + 2) * (X + 2);
   const int rpb = 256 / (C / 8);
   // at least four rounds of rows per workgroup, at most kBnBlocks workgroups
@@ -224,8 +321,33 @@ int bn_sums_impl(bool bwd, const void* y, const void* da, const void* a, const f
   else
     hipLaunchKernelGGL(k_bn_sums<false>, dim3(nblocks), dim3(256), 0, s, py, nullptr,
                        nullptr, nullptr, nullptr, part, M, C, (int)rows);
-  hipLaunchKernelGGL(k_bn_sums_final, dim3((2 * C + 255) / 256), dim3(256), 0, s, part,
+  return nblocks;
+}
+
+int bn_sums_impl(bool bwd, const void* y, const void* da, const void* a, const float* mean,
+                 const float* rstd, float* sums, void* workspace, int B, int C, int Z,
+                 int Y, int X, void* stream) {
+  if (!bn_sums_args_ok(bwd, y, da, a, mean, rstd, workspace, B, C, Z, Y, X) || !sums)
+    return VEON_ERR_BAD_ARG;
+  const int nblocks =
+      bn_sums_stage_one(bwd, y, da, a, mean, rstd, workspace, B, C, Z, Y, X, stream);
+  hipLaunchKernelGGL(k_bn_sums_final, dim3((2 * C + 255) / 256), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const float*>(workspace),
                      sums, 2 * C, nblocks);
+  return launch_status();
+}
+
+int bn_sums_stats_impl(bool bwd, const void* y, const void* da, const void* a,
+                       const float* mean, const float* rstd, double* stats, float* sums32,
+                       void* workspace, int B, int C, int Z, int Y, int X, void* stream) {
+  if (!bn_sums_args_ok(bwd, y, da, a, mean, rstd, workspace, B, C, Z, Y, X) || !stats ||
+      !al8(stats) || (bwd && (!sums32 || !al4(sums32))))
+    return VEON_ERR_BAD_ARG;
+  const int nblocks =
+      bn_sums_stage_one(bwd, y, da, a, mean, rstd, workspace, B, C, Z, Y, X, stream);
+  hipLaunchKernelGGL(k_bn_sums_stats, dim3(2 * C / kStatCols), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const float*>(workspace),
+                     stats, sums32, 2 * C, nblocks, (double)((int64_t)B * Z * Y * X));
   return launch_status();
 }
 
@@ -266,6 +388,55 @@ int veon_bn3d_bwd_sums_bf16(const void* da_padded, const void* a_padded,
                             int X, void* stream) {
   return bn_sums_impl(true, y_padded, da_padded, a_padded, mean, rstd, sums, workspace, B,
                       C, Z, Y, X, stream);
+}
+
+int veon_bn3d_sums_stats_bf16(const void* y_padded, double* stats, void* workspace, int B,
+                              int C, int Z, int Y, int X, void* stream) {
+  return bn_sums_stats_impl(false, y_padded, nullptr, nullptr, nullptr, nullptr, stats,
+                            nullptr, workspace, B, C, Z, Y, X, stream);
+}
+
+int veon_bn3d_bwd_sums_stats_bf16(const void* da_padded, const void* a_padded,
+                                  const void* y_padded, const float* mean,
+                                  const float* rstd, double* stats, float* sums,
+                                  void* workspace, int B, int C, int Z, int Y, int X,
+                                  void* stream) {
+  return bn_sums_stats_impl(true, y_padded, da_padded, a_padded, mean, rstd, stats, sums,
+                            workspace, B, C, Z, Y, X, stream);
+}
+
+int veon_bn_train_coeffs(const double* stats, const float* gamma, const float* beta,
+                         const float* mean_offset, double eps, double momentum,
+                         float* running_mean, float* running_var,
+                         int64_t* num_batches_tracked, float* mean, float* rstd,
+                         float* scale, float* shift, int C, void* stream) {
+  const bool any_running = running_mean || running_var || num_batches_tracked;
+  const bool all_running = running_mean && running_var && num_batches_tracked;
+  if (!bn_channels_ok(C) || !stats || !gamma || !beta || !mean || !rstd || !scale ||
+      !shift || !al8(stats) || !al4(gamma) || !al4(beta) || !al4(mean_offset) ||
+      !al4(mean) || !al4(rstd) || !al4(scale) || !al4(shift) ||
+      (any_running && (!all_running || !al4(running_mean) || !al4(running_var) ||
+                       !al8(num_batches_tracked))) ||
+      !(eps >= 0.0) || !(momentum <= 1.0))
+    return VEON_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_bn_train_coeffs, dim3(1), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), stats, gamma, beta, mean_offset, eps,
+                     momentum, running_mean, running_var, num_batches_tracked, mean, rstd,
+                     scale, shift, C);
+  return launch_status();
+}
+
+int veon_bn_bwd_coeffs(const double* stats, const float* gamma, const float* mean,
+                       const float* rstd, float* ca, float* cb, float* cc, int C,
+                       void* stream) {
+  if (!bn_channels_ok(C) || !stats || !gamma || !mean || !rstd || !ca || !cb || !cc ||
+      !al8(stats) || !al4(gamma) || !al4(mean) || !al4(rstd) || !al4(ca) || !al4(cb) ||
+      !al4(cc))
+    return VEON_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_bn_bwd_coeffs, dim3((C + 255) / 256), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), stats, gamma, mean, rstd, ca, cb, cc,
+                     C);
+  return launch_status();
 }
 
 int veon_bn3d_apply_bf16(const void* y_padded, const float* scale, const float* shift,

@@ -11,7 +11,7 @@ between two kernels is rounded to fp16: loss scaling is the caller's business.
 import torch
 import torch.nn.functional as F
 
-from .. import conv3d_ops, fusion_ops, vit_ops
+from .. import conv3d_ops, fusion_ops, sync_bn, vit_ops
 
 LORA_PAD = 64   # the rank is zero-padded to the GEMM's and the weight gradient's tile width
 
@@ -306,13 +306,21 @@ class _BNReLUTrainFn(torch.autograd.Function):
         y = conv3d_ops.PaddedVolume.from_storage(ys, shape)
         B, C, Z, Y, X = shape
         n = B * Z * Y * X
+        ctx.shape = tuple(shape)
+        # an nn.SyncBatchNorm: the group's statistics (sync_bn.py); the choice and the
+        # group are taken once, here
+        ctx.sync = (sync_bn.group_of(bn),) if sync_bn.is_sync(bn) else None
+        if ctx.sync is not None:
+            mu, r, scale, shift = sync_bn.forward_coeffs(y, bn, ctx.sync[0], mean_offset=bias)
+            a = conv3d_ops.bn_apply(y, scale, shift, relu=True)
+            ctx.save_for_backward(ys, a.storage, mu, r, g, bias)
+            return a.storage
         mean, var, rstd = conv3d_ops.bn_batch_stats(conv3d_ops.bn_sums(y), n, bn.eps)
         conv3d_ops.bn_update_running(
             bn, mean if bias is None else mean + bias.detach().double(), var, n)
         scale = g.detach().double() * rstd
         shift = b.detach().double() - mean * scale
         a = conv3d_ops.bn_apply(y, scale.float(), shift.float(), relu=True)
-        ctx.shape = tuple(shape)
         ctx.save_for_backward(ys, a.storage, mean.float(), rstd.float(), g, bias)
         return a.storage
 
@@ -324,7 +332,11 @@ class _BNReLUTrainFn(torch.autograd.Function):
         vol = conv3d_ops.PaddedVolume.from_storage
         y, a, da = vol(ys, ctx.shape), vol(as_, ctx.shape), vol(dout.contiguous(), ctx.shape)
         n = B * Z * Y * X
-        s = conv3d_ops.bn_bwd_sums(da, a, y, mu, r)
-        dy = conv3d_ops.bn_bwd_apply(da, a, y, *conv3d_ops.bn_bwd_coefficients(s, n, g, mu, r))
+        if ctx.sync is not None:
+            coeffs, s = sync_bn.backward_coeffs(da, a, y, mu, r, g, ctx.sync[0])
+        else:
+            s = conv3d_ops.bn_bwd_sums(da, a, y, mu, r)
+            coeffs = conv3d_ops.bn_bwd_coefficients(s, n, g, mu, r)
+        dy = conv3d_ops.bn_bwd_apply(da, a, y, *coeffs)
         return (dy.storage, s[1].to(g.dtype), s[0].to(g.dtype),
                 torch.zeros_like(bias) if bias is not None and ctx.needs_input_grad[3] else None, None, None)

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ... import _lib, conv3d_ops, vit_ops
+from ... import _lib, conv3d_ops, sync_bn, vit_ops
 from .._native_cache import NativeCacheMixin
 from .._train_fns import LORA_PAD, _BNReLUTrainFn, _half_weight, _rows_linear
 from ... import half as _half
@@ -367,9 +367,18 @@ def semantic_inference_3d_fused(ov_classifier_weight, feat_occ, occ_size):
                                      align_corners=False)
 
 
-def _bn_train_native(y, bn):
+def _bn_sync(bn):
+    """None for a plain BatchNorm; for an nn.SyncBatchNorm the 1-tuple of its process group
+    (``(None,)``: no group, no collective).  Taken once in forward and kept on ``ctx``."""
+    return (sync_bn.group_of(bn),) if sync_bn.is_sync(bn) else None
+
+
+def _bn_train_native(y, bn, sync=None):
     """Batch statistics of the stored conv output ``y`` (PaddedVolume), the update of
-    ``bn``'s buffers, and the fp32 (scale, shift) of the apply pass."""
+    ``bn``'s buffers, and the fp32 (scale, shift) of the apply pass.  ``sync``
+    (``_bn_sync``): the statistics of the whole group (veon_amd/sync_bn.py)."""
+    if sync is not None:
+        return sync_bn.forward_coeffs(y, bn, sync[0])
     B, C, Z, Y, X = y.shape
     n = B * Z * Y * X
     mean, var, rstd = conv3d_ops.bn_batch_stats(conv3d_ops.bn_sums(y), n, bn.eps)
@@ -377,6 +386,17 @@ def _bn_train_native(y, bn):
     scale = bn.weight.detach().double() * rstd
     shift = bn.bias.detach().double() - mean * scale
     return mean.float(), rstd.float(), scale.float(), shift.float()
+
+
+def _bn_bwd_native(da, a, y, mu, r, g, n, sync=None):
+    """The backward sums of one BN and the vectors of ``bn_bwd_apply``: -> (fp32 (2, C)
+    LOCAL sums (dbeta, dgamma), (ca, cb, cc)); with ``sync`` the coefficients come from the
+    group's sums and total count."""
+    if sync is not None:
+        coeffs, s = sync_bn.backward_coeffs(da, a, y, mu, r, g, sync[0])
+        return s, coeffs
+    s = conv3d_ops.bn_bwd_sums(da, a, y, mu, r)
+    return s, conv3d_ops.bn_bwd_coefficients(s, n, g, mu, r)
 
 
 class _ResBlockTrainFn(torch.autograd.Function):
@@ -393,10 +413,11 @@ class _ResBlockTrainFn(torch.autograd.Function):
         x = conv3d_ops.PaddedVolume.from_storage(xs, shape)
         # the half copies of the weights are re-packed from the fp32 parameters every step
         y1 = conv3d_ops.conv3d_k3(x, conv3d_ops.pack_weight(w1))
-        mu1, r1, sc1, sh1 = _bn_train_native(y1, blk.conv1.bn)
+        ctx.sync1, ctx.sync2 = _bn_sync(blk.conv1.bn), _bn_sync(blk.conv2.bn)
+        mu1, r1, sc1, sh1 = _bn_train_native(y1, blk.conv1.bn, ctx.sync1)
         a1 = conv3d_ops.bn_apply(y1, sc1, sh1, relu=True)
         y2 = conv3d_ops.conv3d_k3(a1, conv3d_ops.pack_weight(w2))
-        mu2, r2, sc2, sh2 = _bn_train_native(y2, blk.conv2.bn)
+        mu2, r2, sc2, sh2 = _bn_train_native(y2, blk.conv2.bn, ctx.sync2)
         out = conv3d_ops.bn_apply(y2, sc2, sh2, ident=x, relu=True)
         ctx.shape = tuple(shape)
         ctx.half = half
@@ -416,18 +437,16 @@ class _ResBlockTrainFn(torch.autograd.Function):
         need_x, need_w1, need_w2 = (ctx.needs_input_grad[i] for i in (0, 1, 4))
         # conv2: BN + identity + ReLU backwards, then its two gradients; dz2 (the identity
         # branch's gradient) is stored only when the block's input needs a gradient
-        s2 = conv3d_ops.bn_bwd_sums(da, out, y2, mu2, r2)
-        dy2 = conv3d_ops.bn_bwd_apply(
-            da, out, y2, *conv3d_ops.bn_bwd_coefficients(s2, n, g2, mu2, r2), want_dz=need_x)
+        s2, coeffs2 = _bn_bwd_native(da, out, y2, mu2, r2, g2, n, ctx.sync2)
+        dy2 = conv3d_ops.bn_bwd_apply(da, out, y2, *coeffs2, want_dz=need_x)
         dz2 = None
         if need_x:
             dy2, dz2 = dy2
         dw2 = conv3d_ops.conv3d_k3_wgrad(dy2, a1) if need_w2 else None
         da1 = conv3d_ops.conv3d_k3(dy2, conv3d_ops.pack_weight_dgrad(w2).to(ctx.half))
         # conv1: BN + ReLU backwards
-        s1 = conv3d_ops.bn_bwd_sums(da1, a1, y1, mu1, r1)
-        dy1 = conv3d_ops.bn_bwd_apply(
-            da1, a1, y1, *conv3d_ops.bn_bwd_coefficients(s1, n, g1, mu1, r1))
+        s1, coeffs1 = _bn_bwd_native(da1, a1, y1, mu1, r1, g1, n, ctx.sync1)
+        dy1 = conv3d_ops.bn_bwd_apply(da1, a1, y1, *coeffs1)
         dw1 = conv3d_ops.conv3d_k3_wgrad(dy1, x) if need_w1 else None
         dxs = None
         if need_x:
@@ -450,7 +469,8 @@ class _ConvModuleTrainFn(torch.autograd.Function):
     def forward(ctx, xs, w, g, b, shape, cm):
         x = conv3d_ops.PaddedVolume.from_storage(xs, shape)
         y = conv3d_ops.conv3d_k3(x, conv3d_ops.pack_weight(w))
-        mu, r, sc, sh = _bn_train_native(y, cm.bn)
+        ctx.sync = _bn_sync(cm.bn)
+        mu, r, sc, sh = _bn_train_native(y, cm.bn, ctx.sync)
         a = conv3d_ops.bn_apply(y, sc, sh, relu=True)
         ctx.shape, ctx.half = tuple(shape), _half.dtype()
         ctx.save_for_backward(xs, y.storage, a.storage, mu, r, w, g)
@@ -467,8 +487,8 @@ class _ConvModuleTrainFn(torch.autograd.Function):
         da = vol(dout.contiguous(), oshape)
         n = B * Z * Y * X
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        s = conv3d_ops.bn_bwd_sums(da, a, y, mu, r)
-        dy = conv3d_ops.bn_bwd_apply(da, a, y, *conv3d_ops.bn_bwd_coefficients(s, n, g, mu, r))
+        s, coeffs = _bn_bwd_native(da, a, y, mu, r, g, n, ctx.sync)
+        dy = conv3d_ops.bn_bwd_apply(da, a, y, *coeffs)
         dw = conv3d_ops.conv3d_k3_wgrad(dy, x) if need_w else None
         dxs = None
         if need_x:
@@ -593,7 +613,14 @@ class ResBlock3D(nn.Module):
         volume, the inference path's structure test and the weight gradient's widths
         (both multiples of 64: stricter than ``hip_supported``), BN with buffers."""
         if not (self.hip_train and self.training and torch.is_tensor(x) and x.is_cuda
-                and x.dtype == torch.float32 and x.dim() == 5 and self.hip_supported()):
+                and x.dtype == torch.float32 and x.dim() == 5):
+            return False
+        return self._train_structure_ok()
+
+    def _train_structure_ok(self):
+        """The part of ``_hip_train_ok`` that depends on the module alone (an
+        nn.SyncBatchNorm in place of the BatchNorm3d passes it: sync_bn.py)."""
+        if not self.hip_supported():
             return False
         c1, c2 = self.conv1, self.conv2
         return (conv3d_ops.wgrad_supported(c1.conv.in_channels, c1.conv.out_channels)
