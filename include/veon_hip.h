@@ -1179,6 +1179,31 @@ int veon_occ_confusion(const void *pred, int pred_elem_bytes, const uint8_t *gt,
                        const uint8_t *mask, int64_t n, int n_cl, int64_t *hist, int *flag,
                        void *stream);
 
+/* ======== occ_fscore.hip ============================================================ */
+
+/* The counts of Metric_FScore (mmdet3d/datasets/occ_metrics.py:150-237) without its
+ * KD-trees: both point sets are voxel centres of one lattice, so "nearest neighbour
+ * closer than the threshold" is an integer stencil (veon_amd/occ_eval.py: fscore_reach).
+ * pred: labels (B,X,Y,Z) of pred_elem_bytes = 1 (uint8) or 8 (int64); gt, mask (NULL = no
+ * mask): uint8 of the same shape; 1 <= Z <= 64, B*X*Y*Z < 2^31.  A voxel is OCCUPIED
+ * when its mask is not 0 and its label is not void; void_words: a HOST array of four
+ * 64-bit words, bit v % 64 of word v / 64 set = label v is void; an int64 label outside
+ * [0, 255] is occupied.  reach_acc / reach_cmpl: HOST arrays of (2r + 1)^2 ints, r =
+ * r_acc / r_cmpl in [0, 3]: entry (dx + r)*(2r + 1) + dy + r is the largest |dz| at which
+ * offset (dx, dy, dz) counts as near, in [0, 63], or -1 for none.  Added to
+ * counts[4*b ..] (B*4 int64, accumulated into, never cleared):
+ *   n_pred, n_gt   occupied voxels of pred / gt in sample b
+ *   hit_pred       occupied pred voxels with an occupied gt voxel near (reach_acc)
+ *   hit_gt         occupied gt voxels with an occupied pred voxel near (reach_cmpl)
+ * Voxels outside the sample's grid are empty.  Nothing is written to the inputs (the
+ * reference overwrites masked voxels of its arguments with 255).  Integer atomics:
+ * exact, the same for every run.  Nothing is allocated or read back. */
+int veon_occ_fscore_counts(const void *pred, int pred_elem_bytes, const uint8_t *gt,
+                           const uint8_t *mask, int B, int X, int Y, int Z,
+                           const int64_t *void_words, int r_acc, const int *reach_acc,
+                           int r_cmpl, const int *reach_cmpl, int64_t *counts,
+                           void *stream);
+
 /* ======== occ_retrieval.hip ========================================================= */
 
 /* Open-vocabulary point retrieval, the `retrieval=True` branch of

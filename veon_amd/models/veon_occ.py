@@ -526,7 +526,17 @@ class VeonOccupancyPath(nn.Module):
         the B samples against ``voxel_semantics`` (B, X, Y, Z) added to ``metric.hist``
         (an ``occ_eval.OccMiouMetric`` on the images' device) by the tail kernel
         itself; ``mask_camera`` (B, X, Y, Z) is applied when the metric uses the image
-        mask.  Nothing is read back.  -> the uint8 labels (B, X, Y, Z)."""
+        mask.  Nothing is read back.  -> the uint8 labels (B, X, Y, Z).
+
+        ``metric`` may also be an ``occ_eval.OccFScoreMetric`` (``Metric_FScore``,
+        occ_metrics.py:190-233), or a list or tuple of metrics with at most one
+        ``OccMiouMetric``: that one keeps its fused histogram, the same call with the same
+        result as alone; every F-score metric gets ``add_batch`` of the returned labels
+        on the device, with the camera mask when it uses the image mask."""
+        from ..occ_eval import OccFScoreMetric
+        if isinstance(metric, (list, tuple, OccFScoreMetric)):
+            return self._evaluate_many(images, img_metas, voxel_semantics, mask_camera,
+                                       metric, prev_volumes, depth)
         n_cl = self.ov_classifier_weight.shape[0] + 1
         if metric.num_classes != n_cl:
             raise ValueError('the metric counts %d classes, the path predicts %d (+ free)'
@@ -546,6 +556,35 @@ class VeonOccupancyPath(nn.Module):
                             count)
         metric.cnt += images.shape[0]
         return out['occ_pred_cls']
+
+    def _evaluate_many(self, images, img_metas, voxel_semantics, mask_camera, metrics,
+                       prev_volumes, depth):
+        """``evaluate`` with F-score metrics beside (or without) the mIoU metric."""
+        from ..occ_eval import OccFScoreMetric
+        metrics = list(metrics) if isinstance(metrics, (list, tuple)) else [metrics]
+        fscores = [m for m in metrics if isinstance(m, OccFScoreMetric)]
+        mious = [m for m in metrics if not isinstance(m, OccFScoreMetric)]
+        if not metrics or len(mious) > 1:
+            raise ValueError('evaluate() takes at most one OccMiouMetric and any number of '
+                             'OccFScoreMetric, got %d and %d' % (len(mious), len(fscores)))
+        for m in fscores:    # before anything is counted
+            if m.device != images.device:
+                raise ValueError('the metric lives on %s, the images on %s'
+                                 % (m.device, images.device))
+            if m.use_lidar_mask and not m.use_image_mask:
+                raise ValueError('evaluate() takes the camera mask only')
+            if m.use_image_mask and mask_camera is None:
+                raise ValueError('the metric applies the camera mask but none was given')
+        if mious:
+            labels = self.evaluate(images, img_metas, voxel_semantics, mask_camera, mious[0],
+                                   prev_volumes, depth)
+        else:
+            with torch.no_grad():
+                labels = self._run(images, img_metas, prev_volumes, depth, False, False,
+                                   True)['occ_pred_cls']
+        for m in fscores:
+            m.add_batch(labels, voxel_semantics, None, mask_camera)
+        return labels
 
     def _run(self, images, img_metas, prev_volumes, depth, with_2d, return_features,
              labels_only, count=None):
