@@ -1385,6 +1385,37 @@ int veon_depth_loss_reduce(int64_t rows, const float *rec, float *out, float *co
 int veon_depth_loss_bwd(int BN, int Hp, int Wp, int sp, const float *rec, const float *coef,
                         const float *g_zoe, const float *g_ce, float *grad, void *stream);
 
+/* ======== lidar_depth.hip =========================================================== */
+
+/* The LiDAR depth labels of the depth pre-training stage, PointToMultiViewDepth
+ * (datasets/pipelines/loading.py:735-759 points2depthmap, :811-821 the projection), as the
+ * exact minimum kept depth per pixel, or per block x block pixels.
+ * points (B,P,row_stride) fp32, row_stride >= 3 floats, the first three of a row are read;
+ * lidar2img (B,N,3,4) fp32 (rows R | t of the 4x4's upper three), post_rots (B,N,3,3),
+ * post_trans (B,N,3); out (B,N,H/block,W/block) fp32, all contiguous.  H x W is the map
+ * AFTER `downsample`; block in {1, 2, 4, 8, 16} divides both; 0 < lo < hi; 1 <= B <= 65535,
+ * B*P <= 2^31 - 1, H, W <= 2^24; otherwise VEON_ERR_BAD_ARG.  P = 0 is allowed.
+ *
+ * Per point and camera, fp32, one rounding per operation in this order:
+ *   q = (R p) + t;  (u, v, d) = post_rot (q.x / q.z, q.y / q.z, q.z) + post_tran
+ *   x = rint(u / downsample), y = rint(v / downsample)   (round-half-to-even: torch.round)
+ *   kept iff x >= 0, x < W, y >= 0, y < H, d < hi, d >= lo, all tested in floating point:
+ *   NaN, infinities, q.z = 0 and huge coordinates fail a comparison; x = -0.0 is pixel 0.
+ * lidar2img == NULL: the rows are image points (u, v, d) already (points2depthmap alone),
+ * post_rots / post_trans are not read and N must be 1.
+ *
+ * out[b][n][y / block][x / block] = the smallest kept d, 0 where nothing landed.  Kept
+ * depths are positive, so their bit patterns order as their values: an unsigned atomic
+ * minimum on out's own storage, exact and independent of the point order (repeated calls
+ * and permuted points give the same bits).  EVERY element of out is written; no workspace,
+ * no read-back, three launches (two when P = 0) on `stream`, capturable.  For hi <= 1e5
+ * the block result equals downsample_depth(block = 1 result, block) with that function's
+ * 1e5 for an empty block read as 0, bit for bit. */
+int veon_lidar_depth_render(const float *points, int B, int P, int row_stride,
+                            const float *lidar2img, const float *post_rots,
+                            const float *post_trans, int N, int H, int W, int downsample,
+                            int block, float lo, float hi, float *out, void *stream);
+
 /* ======== occ_bin_loss.hip ========================================================== */
 
 /* The occupancy term of the training loss, BCE_BinOcc_Loss

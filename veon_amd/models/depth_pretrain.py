@@ -4,6 +4,8 @@ encoder, DPT head) against LiDAR depth.
 
     forward_train(img_inputs, depth_img_inputs, gt_depth) -> {'loss_depth_zoe',
                                                               'loss_depth_ce'}
+    forward_train(img_inputs, depth_img_inputs, points=...)   the same, the LiDAR depth
+                                                              rendered here
 
 ``estimate_depth`` (:157-166) runs the estimator and resizes its metric depth to half the
 image (bilinear, align_corners=True; torch).  ``forward_train`` (:128-154) downsamples
@@ -18,7 +20,15 @@ and the ``NotImplementedError`` test stubs are not mirrored (call ``forward_trai
 ``hip_train`` (default False): opt-in native training path.  It switches on the DINOv2
 blocks' ``hip_train`` (depth_anything/dinov2.py) and computes the loss with
 csrc/depth_loss.hip (no host synchronisation); off, the loss is the reference's torch
-sequence."""
+sequence.
+
+``points`` (the reference's signature has the keyword and ignores it): when ``gt_depth``
+is None the LiDAR depth is rendered from the sweeps and the eleven-entry ``img_inputs``
+(veon_amd/lidar_depth.py, the pipeline step ``PointToMultiViewDepth`` at downsample 1).
+With ``hip_train`` on a ROCm device it is rendered natively at the block size
+``gt_depth_scale``, the 1/256 of the full maps that the loss reads, and the loss takes it
+at scale 1: the same loss bits as the full maps at ``gt_depth_scale``.  Otherwise the full
+maps come from the torch mirror.  With ``gt_depth`` given nothing changes."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -26,6 +36,7 @@ import torch.nn.functional as F
 from .builder import build_neck
 from .depth_anything.dinov2 import Block
 from .. import depth_loss
+from ..lidar_depth import PointToMultiViewDepth, pad_points
 
 
 def _build(cfg):
@@ -85,18 +96,31 @@ class VeonDepthPretrain(nn.Module):
         dout['metric_depth'] = abs_depth.view(B, N, *abs_depth.shape[-2:])
         return dout
 
-    def forward_train(self, img_inputs=None, depth_img_inputs=None, gt_depth=None, **kwargs):
+    def forward_train(self, img_inputs=None, depth_img_inputs=None, gt_depth=None,
+                      points=None, **kwargs):
         h, w = img_inputs[0].shape[-2:]
         depth = self.estimate_depth(depth_img_inputs, (h // 2, w // 2))['metric_depth']
         vt = self.img_view_transformer
+        native = self.hip_train and depth.is_cuda
+        gt_scale = self.gt_depth_scale
+        if gt_depth is None:
+            if points is None:
+                raise ValueError('forward_train needs gt_depth or points')
+            to_depth = PointToMultiViewDepth(vt.grid_config, downsample=1)
+            points = pad_points(points).to(device=depth.device, dtype=torch.float32)
+            if native:
+                gt_depth = to_depth.render(points.contiguous(), img_inputs, block=gt_scale)
+                gt_scale = 1
+            else:
+                gt_depth = to_depth.render(points, img_inputs, mirror=True)
         depth, gt_depth = depth.float(), gt_depth.float()          # @force_fp32 (:496)
-        if self.hip_train and depth.is_cuda:
+        if native:
             losses = vt.depth_pretrain_loss(depth.contiguous(), gt_depth.contiguous(),
-                                            self.pred_depth_scale, self.gt_depth_scale)
+                                            self.pred_depth_scale, gt_scale)
         else:
             lo, _, step = vt.grid_config['depth']
             losses = depth_loss.depth_pretrain_loss_torch(
-                depth, gt_depth, vt.D, lo, step, self.pred_depth_scale, self.gt_depth_scale)
+                depth, gt_depth, vt.D, lo, step, self.pred_depth_scale, gt_scale)
         depth_error = losses.pop('depth_error')
         # running mean over the steps (:146-147), kept on the device
         self.avg_depth_error.mul_(self.nonce).add_(depth_error.to(self.avg_depth_error.dtype)) \
