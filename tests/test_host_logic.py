@@ -474,3 +474,36 @@ def test_padded_grid_geometry(cls, shape):
     wide = g.like(16)
     assert type(wide) is Grid and wide.shape == (B, 16, *spatial) and not wide.storage.any()
     assert g.like().shape == g.shape and g.like().storage is not g.storage
+
+
+def _read_back(p, ctype, n):
+    return list(ctypes.cast(p, ctypes.POINTER(ctype))[:n])
+
+
+@pytest.mark.parametrize('kind', ['permuted', 'expanded'])
+def test_strides_pointer_outlives_the_python_temporaries(kind):
+    """``_lib.strides(t)`` is the only reference to its int64 array: what stands behind the
+    pointer must still be ``t.stride()`` after a collection."""
+    import gc
+    if kind == 'permuted':
+        t = torch.empty(2, 3, 4, 5, 6).permute(0, 4, 2, 1, 3)
+    else:
+        t = torch.empty(2, 1, 4, 1, 6).expand(2, 3, 4, 5, 6)
+        assert 0 in t.stride()
+    p = _lib.strides(t)
+    want = list(t.stride())
+    del t
+    junk = [(ctypes.c_int64 * 5)(*([-1] * 5)) for _ in range(64)]   # reuse of a freed block
+    del junk
+    gc.collect()
+    assert isinstance(p, ctypes.c_void_p) and p.value
+    assert _read_back(p, ctypes.c_int64, 5) == want
+
+
+def test_host_array_round_trips_other_element_types():
+    import gc
+    ints = _lib.host_array([3, -1, 0, 2 ** 31 - 1], ctypes.c_int)
+    floats = _lib.host_array((0.5, -2.25, 1e-3), ctypes.c_float)
+    gc.collect()
+    assert _read_back(ints, ctypes.c_int, 4) == [3, -1, 0, 2 ** 31 - 1]
+    assert _read_back(floats, ctypes.c_float, 3) == [np.float32(v) for v in (0.5, -2.25, 1e-3)]

@@ -176,6 +176,18 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def host_array(values, ctype=ctypes.c_int64):
+    """A small host array of ``ctype`` as a pointer argument of ``launch``.  The c_void_p
+    keeps the array alive (ctypes.cast records its source in the result's ``_objects``)."""
+    values = list(values)
+    return ctypes.cast((ctype * len(values))(*values), ctypes.c_void_p)
+
+
+def strides(t):
+    """``t.stride()`` as the host ``int64_t[t.dim()]`` argument of the strided entry points."""
+    return host_array(t.stride())
+
+
 def stream_ptr(device):
     """PyTorch's current stream on ``device`` as a raw hipStream_t (no Stream
     object is built: this sits on every launch)."""

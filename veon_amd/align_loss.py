@@ -10,8 +10,6 @@ loss that reads the feature at a few percent of the voxels.  On a ROCm device
 ``voxel_cosine`` is native in both directions (csrc/occ_align_loss.hip) and reads and
 writes the LOW-resolution volume only; on CPU it runs the reference sequence in torch
 (upsample, gather, cosine), which is the CPU tests' oracle."""
-import ctypes
-
 import torch
 import torch.nn.functional as F
 
@@ -69,10 +67,6 @@ def _reference(feat_low, voxels, labels, table, occ_size, eps, batch):
     return F.cosine_similarity(f, t, dim=1, eps=eps)
 
 
-def _strides(t):
-    return ctypes.cast((ctypes.c_int64 * 5)(*t.stride()), ctypes.c_void_p)
-
-
 class _VoxelCosine(torch.autograd.Function):
     """The native pair veon_occ_align_fwd / veon_occ_align_bwd."""
 
@@ -95,7 +89,7 @@ class _VoxelCosine(torch.autograd.Function):
         cos = torch.empty((N,), dtype=torch.float32, device=dev)
         stats = torch.empty((N, 2), dtype=torch.float32, device=dev)
         tnorm = torch.empty((K,), dtype=torch.float32, device=dev)
-        _lib.launch('veon_occ_align_fwd', dev, feat, _strides(feat), C, feat.shape[0], zi, yi,
+        _lib.launch('veon_occ_align_fwd', dev, feat, _lib.strides(feat), C, feat.shape[0], zi, yi,
                     xi, Zo, Yo, Xo, vox, lab, N, kb, tab, K, eps, tnorm, cos, stats)
         ctx.save_for_backward(feat, vox, lab, tab, tnorm, stats)
         ctx.occ_size, ctx.eps, ctx.batch, ctx.kb, ctx.B = occ_size, eps, batch, kb, B
@@ -145,7 +139,7 @@ class _VoxelCosine(torch.autograd.Function):
             occ_rows[uniq] = torch.arange(M, dtype=torch.int32, device=dev)
             order = order.to(torch.int32)
             rows = torch.empty((M, C), dtype=torch.float32, device=dev)
-        _lib.launch('veon_occ_align_bwd', dev, feat, _strides(feat), C, feat.shape[0], zi, yi, xi,
+        _lib.launch('veon_occ_align_bwd', dev, feat, _lib.strides(feat), C, feat.shape[0], zi, yi, xi,
                     vox, lab, N, ctx.kb, tab, K, ctx.eps, tnorm, stats, g, order, seg, M, occ_rows,
                     rows, buf[ctx.batch])
         return (buf.permute(0, 4, 1, 2, 3),) + (None,) * 6

@@ -188,11 +188,10 @@ def _native(sem_seg, img_inputs, labels, class_reflection, priority, grid_config
     cams = torch.cat([ego2img[:, :3].reshape(n_cam, 12), post_rots.reshape(n_cam, 9),
                       post_trans.reshape(n_cam, 3)], 1).contiguous()
     gc = grid_config
-    grid = (ctypes.c_float * 10)(
-        gc['x'][2], gc['x'][0] + gc['x'][2] / 2, gc['y'][2], gc['y'][0] + gc['y'][2] / 2,
-        gc['z'][2], gc['z'][0] + gc['z'][2] / 2, width - 1, height - 1,
-        gc['depth'][0], gc['depth'][1])
-    grid_p = ctypes.cast(grid, ctypes.c_void_p)
+    grid_p = _lib.host_array(
+        [gc['x'][2], gc['x'][0] + gc['x'][2] / 2, gc['y'][2], gc['y'][0] + gc['y'][2] / 2,
+         gc['z'][2], gc['z'][0] + gc['z'][2] / 2, width - 1, height - 1,
+         gc['depth'][0], gc['depth'][1]], ctypes.c_float)
 
     gid_list, _ = group_ids(class_reflection)
     gid = _constant(dev, 'gid', gid_list, torch.int32)

@@ -5,6 +5,7 @@
 implicit-GEMM conv consumes and produces.  Everything launches on the current
 stream; there is no CPU path.
 """
+import ctypes
 import math
 
 import torch
@@ -125,7 +126,6 @@ def sigm_bwd_pack_cl(grad, f, out=None):
     (B, C, Z, Y, X) with channel stride 1 (any outer strides), ``f`` the stored half output
     (PaddedVolume) -> d pre = grad * (0.25 - f^2) as a PaddedVolume whose every row is
     stored, halo and guard rows as zeros (``out``: an existing volume to overwrite)."""
-    import ctypes
     dev = _lib.require_device(grad, f.storage)
     _lib.require_half(f.storage)
     B, C, Z, Y, X = f.shape
@@ -136,9 +136,9 @@ def sigm_bwd_pack_cl(grad, f, out=None):
     if out is None:
         out = PaddedVolume.from_storage(torch.empty_like(f.storage), f.shape)
     assert out.shape == f.shape and out is not f
-    st = (ctypes.c_int64 * 4)(grad.stride(0), grad.stride(2), grad.stride(3), grad.stride(4))
-    _lib.launch('veon_volume_sigm_bwd_pack_cl', dev, grad, ctypes.cast(st, ctypes.c_void_p),
-                f.storage, out.storage, f.guard, B, C, Z, Y, X)
+    st = _lib.host_array([grad.stride(0), grad.stride(2), grad.stride(3), grad.stride(4)])
+    _lib.launch('veon_volume_sigm_bwd_pack_cl', dev, grad, st, f.storage, out.storage,
+                f.guard, B, C, Z, Y, X)
     return out
 
 
@@ -619,7 +619,6 @@ def warp_volume(vol, affine, out=None):
 def warp_affine(cur2glob, prev2glob, first_xyz, step_xyz):
     """(B,1,4,4) or (B,4,4) ROCm fp32 ego->global transforms of the current and a
     past frame -> (B,3,4) voxel-index map for ``warp_volume`` (no host sync)."""
-    import ctypes
     dev = _lib.require_device(cur2glob, prev2glob)
     mats = []
     for m in (cur2glob, prev2glob):
@@ -630,8 +629,8 @@ def warp_affine(cur2glob, prev2glob, first_xyz, step_xyz):
     B = mats[0].shape[0]
     assert tuple(mats[0].shape) == tuple(mats[1].shape) == (B, 4, 4)
     out = torch.empty((B, 3, 4), dtype=torch.float32, device=dev)
-    first = (ctypes.c_double * 3)(*[float(v) for v in first_xyz])
-    step = (ctypes.c_double * 3)(*[float(v) for v in step_xyz])
+    first = _lib.host_array([float(v) for v in first_xyz], ctypes.c_double)
+    step = _lib.host_array([float(v) for v in step_xyz], ctypes.c_double)
     _lib.launch('veon_warp_affine', dev, mats[0], mats[1], 16, first, step, out, B)
     return out
 
@@ -930,7 +929,6 @@ def occ_classify(sem_low, bin_low, occ_size):
     (B,Q,z,y,x) and occupancy logits ``bin_low`` (B,2,z,y,x) -- fp32, ANY strides --
     to ``occ_size``, plus the label volume of VEONTemporal.simple_test, in one kernel.
     -> (sem_occ (B,Q,Z,Y,X), bin_occ (B,2,Z,Y,X), occ_pred_cls (B,X,Y,Z) int64)."""
-    import ctypes
     dev = _lib.require_device(sem_low, bin_low)
     assert sem_low.dtype == bin_low.dtype == torch.float32
     B, Q, zi, yi, xi = sem_low.shape
@@ -939,9 +937,6 @@ def occ_classify(sem_low, bin_low, occ_size):
     sem = torch.empty((B, Q, Zo, Yo, Xo), dtype=torch.float32, device=dev)
     binv = torch.empty((B, 2, Zo, Yo, Xo), dtype=torch.float32, device=dev)
     cls = torch.empty((B, Xo, Yo, Zo), dtype=torch.int64, device=dev)
-    s5 = ctypes.c_int64 * 5
-    ss, bs = s5(*sem_low.stride()), s5(*bin_low.stride())
-    _lib.launch('veon_occ_classify', dev, sem_low, ctypes.cast(ss, ctypes.c_void_p), Q,
-                bin_low, ctypes.cast(bs, ctypes.c_void_p), B, zi, yi, xi, Zo, Yo, Xo,
-                sem, binv, cls)
+    _lib.launch('veon_occ_classify', dev, sem_low, _lib.strides(sem_low), Q, bin_low,
+                _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, sem, binv, cls)
     return sem, binv, cls

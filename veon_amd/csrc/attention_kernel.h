@@ -364,6 +364,7 @@ __global__ __launch_bounds__(256, (HAS_BIAS && STATS) ? 2 : 3) void k_attention(
     if (STATS) {   // before the `continue`: every lane takes part in the exchange
       // the four lane rows of a query hold 16 keys of a tile each
       float lf = lsum[i][0] + lsum[i][1];
+      // (16 then 32, low to high: written out, a helper changed the code)
       lf += __shfl_xor(lf, 16);
       lf += __shfl_xor(lf, 32);
       if (q < T && fg == 0) {

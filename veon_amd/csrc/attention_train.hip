@@ -71,6 +71,7 @@ __global__ __launch_bounds__(256) void k_attention_delta(
     acc = fmaf(bf2f((bf16_t)(a.y & 0xffffu)), bf2f((bf16_t)(g.y & 0xffffu)), acc);
     acc = fmaf(bf2f((bf16_t)(a.y >> 16)), bf2f((bf16_t)(g.y >> 16)), acc);
   }
+  // (16-lane groups by shuffle width: no shared helper has this form)
 #pragma unroll
   for (int m = 8; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 16);
   if (r < rows && part == 0) {
@@ -325,6 +326,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_bwd(
 #pragma unroll
     for (int i = 0; i < QT; ++i) {
       float d = del_o[i], l = psum[i];
+      // (16 then 32, low to high: written out, a helper changed the code)
       d += __shfl_xor(d, 16);
       d += __shfl_xor(d, 32);
       l += __shfl_xor(l, 16);

@@ -27,7 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/veon_hip.h"
+#include "host_common.h"
 #include "half_mode.h"
 
 namespace {
@@ -44,10 +44,6 @@ int g_pool_workers = 0, g_pool_cold = 0, g_pool_warm = 0;  // 0 = built-in defau
 // fused 165 -> 157 us fp32 rows, 135 -> 128.5 us bf16 rows with runs of 32 tiles; the
 // max-pool kernel (and the S2 slab kernel) gain nothing measurable
 constexpr int kOrderCf = 5, kOrderMp = -1;
-
-inline int launch_status() {
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
-}
 
 __device__ __forceinline__ int rl(int v, int lane) {
   return __builtin_amdgcn_readlane(v, lane);
@@ -893,6 +889,7 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_rows_maxpool_bwd(
             if constexpr (DG) {
               float sdot = chact ? (m0 * f.x + m1 * f.y) + (m2 * f.z + m3 * f.w) : 0.f;
 #pragma unroll
+              // (the order of wave_sum in lane_reduce.h, written out)
               for (int o = 32; o >= 1; o >>= 1) sdot += __shfl_xor(sdot, o);
               if (lane == i + u) dacc = sdot;
             }
@@ -1136,10 +1133,6 @@ __global__ __launch_bounds__(NW * 64) void k_rows_fused_cf(
   }
 }
 
-inline bool aligned16(const void* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1254,7 +1247,7 @@ int rows_maxpool_launch(
     return VEON_ERR_BAD_ARG;
   if ((int64_t)batch * Z * Y * X > 0x7ffffffeLL) return VEON_ERR_BAD_ARG;
   if (feat_elems <= 0 || feat_elems > 0x7fffffffLL) return VEON_ERR_BAD_ARG;  // 32-bit rows
-  if (!aligned16(feat) || (reinterpret_cast<uintptr_t>(out) & 7u))
+  if (!aligned(feat, 16) || (reinterpret_cast<uintptr_t>(out) & 7u))
     return VEON_ERR_BAD_ARG;
   const int64_t plane = (int64_t)(Z / dz) * (Y / dy) * (X / dx);
   if (plane * batch > 0x7fffffffLL) return VEON_ERR_BAD_ARG;
@@ -1354,7 +1347,7 @@ int veon_bev_pool_v2_bwd_rows_maxpool(int c, int n_images, int D, int HW, int ba
     return VEON_ERR_BAD_ARG;
   if ((int64_t)batch * Z * Y * X > 0x7ffffffeLL) return VEON_ERR_BAD_ARG;
   if ((int64_t)n_images * D * HW > 0x7fffffffLL) return VEON_ERR_BAD_ARG;
-  if (!aligned16(pooled_grad) || !aligned16(feat) || !aligned16(feat_grad) ||
+  if (!aligned(pooled_grad, 16) || !aligned(feat, 16) || !aligned(feat_grad, 16) ||
       (reinterpret_cast<uintptr_t>(winner) & 3u))
     return VEON_ERR_BAD_ARG;
   const int64_t n_pix = (int64_t)n_images * HW;

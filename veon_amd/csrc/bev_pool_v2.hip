@@ -15,8 +15,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/veon_hip.h"
+#include "host_common.h"
 #include "half_mode.h"
+#include "lane_reduce.h"
 
 extern "C" int veon_pool_debug_flags;  // bev_pool_rows.hip
 
@@ -285,10 +286,7 @@ __device__ __forceinline__ TileInfo tile_info(int64_t t, int64_t tiles_per_batch
 // Occupancy mask of a tile: bit v set iff voxel v of the tile has an interval.
 // Column of an occupied voxel = number of occupied voxels below it = index of
 // its interval inside the tile (intervals are ascending in voxel rank).
-__device__ __forceinline__ unsigned long long wave_or(unsigned long long bit) {
-  for (int off = 32; off > 0; off >>= 1) bit |= __shfl_xor(bit, off);
-  return bit;
-}
+// (the masks of the lanes are combined by wave_or of lane_reduce.h)
 
 // ---------------------------------------------------------------------------
 // (2) Fused forward, channels-last (B,Z,Y,X,C): a tile is one contiguous
@@ -664,14 +662,6 @@ __global__ __launch_bounds__(kBwdBlock) void k_pool_bwd(
   }
 }
 
-inline int launch_status() {
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
-}
-
-inline bool aligned16(const void* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
-
 }  // namespace
 
 // (B*N, C, H*W) -> (B*N, H*W, C): the `feat.permute(0,1,3,4,2).contiguous()` in
@@ -784,7 +774,7 @@ int veon_bev_pool_v2_fwd(int c, int n_intervals, const float* depth,
   PoolArgs a{depth, feat, ranks_depth, ranks_feat, ranks_bev, interval_starts,
              interval_lengths};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool v4 = (c % 4 == 0) && aligned16(feat) && aligned16(out);
+  const bool v4 = (c % 4 == 0) && aligned(feat, 16) && aligned(out, 16);
   const int cq = v4 ? c / 4 : c;
   const int64_t threads = (int64_t)n_intervals * cq;
   const int64_t blocks = (threads + kBlock - 1) / kBlock;
@@ -813,7 +803,7 @@ int veon_bev_pool_v2_bwd(int c, int n_intervals, const float* out_grad,
   PoolArgs a{depth, feat, ranks_depth, ranks_feat, ranks_bev, interval_starts,
              interval_lengths};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool v4 = (c % 4 == 0) && aligned16(feat) && aligned16(out_grad);
+  const bool v4 = (c % 4 == 0) && aligned(feat, 16) && aligned(out_grad, 16);
   if (v4)
     hipLaunchKernelGGL(k_pool_bwd<4>, dim3((unsigned)n_intervals),
                        dim3(kBwdBlock), 0, s, a, c, n_intervals, out_grad,
@@ -927,14 +917,14 @@ static int maxpool_impl(bool padded, int c, int n_intervals, int batch, int Z,
                          dz, dy, dx, out);                                    \
   } while (0)
   if (feat_dtype == VEON_FEAT_F32) {
-    if ((c % 4 == 0) && (cs % 4 == 0) && aligned16(feat))
+    if ((c % 4 == 0) && (cs % 4 == 0) && aligned(feat, 16))
       VEON_LAUNCH_MP(4, FeatF32);
     else
       VEON_LAUNCH_MP(1, FeatF32);
   } else {
     // 16-byte gathers (8 channels per lane) pay at VEON's C = 256; at C = 80
     // they leave too few lanes busy and 8-byte gathers are faster (measured)
-    const bool v4 = (c % 4 == 0) && (cs % 4 == 0) && aligned16(feat);
+    const bool v4 = (c % 4 == 0) && (cs % 4 == 0) && aligned(feat, 16);
     const bool v8 = v4 && (c % 8 == 0) && (cs % 8 == 0) && c >= 128;
     if (feat_dtype == VEON_FEAT_F16) {
       if (v8) VEON_LAUNCH_MP(8, FeatF16);
@@ -1029,7 +1019,7 @@ static int fused_impl(int c, int n_intervals, int batch, int64_t voxels_per_batc
   const int4* plan4 = reinterpret_cast<const int4*>(plan);
   if (out_layout == VEON_LAYOUT_BZYXC) {
     // lanes = (voxel, 4 channels) so that stores stay 16 bytes per lane
-    const bool v4 = (c % 4 == 0) && aligned16(feat) && aligned16(out);
+    const bool v4 = (c % 4 == 0) && aligned(feat, 16) && aligned(out, 16);
 #define VEON_LAUNCH_CL(VEC, FT)                                                \
   hipLaunchKernelGGL((k_pool_fused_cl<VEC, FT>), dim3((unsigned)n_tiles),      \
                      dim3(kBlock), 0, s, a, plan4, c, c / VEC,                 \
@@ -1062,12 +1052,12 @@ static int fused_impl(int c, int n_intervals, int batch, int64_t voxels_per_batc
 #define VEON_LAUNCH_CF2(VEC, FT) \
   do { if (dense) VEON_LAUNCH_CF(VEC, 64, FT); else VEON_LAUNCH_CF(VEC, 32, FT); } while (0)
   if (feat_dtype == VEON_FEAT_F32) {
-    if ((c % 4 == 0) && aligned16(feat)) VEON_LAUNCH_CF2(4, FeatF32);
+    if ((c % 4 == 0) && aligned(feat, 16)) VEON_LAUNCH_CF2(4, FeatF32);
     else VEON_LAUNCH_CF2(1, FeatF32);
   } else {
     // 4 channels (8 bytes) per lane: the kernel is latency-, not byte-bound,
     // and 8 channels per lane halve the lanes in flight (measured slower)
-    const bool v4 = (c % 4 == 0) && (cs % 4 == 0) && aligned16(feat);
+    const bool v4 = (c % 4 == 0) && (cs % 4 == 0) && aligned(feat, 16);
     if (feat_dtype == VEON_FEAT_F16) {
       if (v4) VEON_LAUNCH_CF2(4, FeatF16); else VEON_LAUNCH_CF2(1, FeatF16);
     } else {

@@ -150,15 +150,10 @@ __global__ __launch_bounds__(256) void k_image_layernorm_bwd(
     }
     store_row<N>(dx + m * C, lane, has, d);
   }
-  if (wave > 0) {
-#pragma unroll
-    for (int k = 0; k < 3 * E; ++k) red[wave - 1][k * 64 + lane] = acc[k];
-  }
-  __syncthreads();
+  park_waves<3 * E>(acc, red, lane, wave);
   if (wave == 0) {
 #pragma unroll
-    for (int k = 0; k < 3 * E; ++k)
-      acc[k] = ((acc[k] + red[0][k * 64 + lane]) + red[1][k * 64 + lane]) + red[2][k * 64 + lane];
+    for (int k = 0; k < 3 * E; ++k) acc[k] = add_waves_in_order(acc[k], red, k * 64 + lane);
     float* o = part + (int64_t)blockIdx.x * 3 * C;
 #pragma unroll
     for (int s = 0; s < 3; ++s)

@@ -737,6 +737,7 @@ __global__ __launch_bounds__(256) void k_image_layernorm(
       sum += v[k] + v[8 + k];
     }
   }
+  // (written out, not wave_sum of lane_reduce.h: the call changes this kernel's code)
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
   const float mean = sum / C;

@@ -290,8 +290,6 @@ __global__ __launch_bounds__(256) void k_bn_bwd_coeffs(
   cc[c] = (float)(-g * r * stats[c] / n - b * mu);
 }
 
-inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 bool bn_channels_ok(int C) { return C > 0 && C % 8 == 0 && C <= 2048; }
 
 bool bn_sums_args_ok(bool bwd, const void* y, const void* da, const void* a,
@@ -341,7 +339,7 @@ int bn_sums_stats_impl(bool bwd, const void* y, const void* da, const void* a,
                        const float* mean, const float* rstd, double* stats, float* sums32,
                        void* workspace, int B, int C, int Z, int Y, int X, void* stream) {
   if (!bn_sums_args_ok(bwd, y, da, a, mean, rstd, workspace, B, C, Z, Y, X) || !stats ||
-      !al8(stats) || (bwd && (!sums32 || !al4(sums32))))
+      !aligned(stats, 8) || (bwd && (!sums32 || !aligned(sums32, 4))))
     return VEON_ERR_BAD_ARG;
   const int nblocks =
       bn_sums_stage_one(bwd, y, da, a, mean, rstd, workspace, B, C, Z, Y, X, stream);
@@ -413,10 +411,11 @@ int veon_bn_train_coeffs(const double* stats, const float* gamma, const float* b
   const bool any_running = running_mean || running_var || num_batches_tracked;
   const bool all_running = running_mean && running_var && num_batches_tracked;
   if (!bn_channels_ok(C) || !stats || !gamma || !beta || !mean || !rstd || !scale ||
-      !shift || !al8(stats) || !al4(gamma) || !al4(beta) || !al4(mean_offset) ||
-      !al4(mean) || !al4(rstd) || !al4(scale) || !al4(shift) ||
-      (any_running && (!all_running || !al4(running_mean) || !al4(running_var) ||
-                       !al8(num_batches_tracked))) ||
+      !shift || !aligned(stats, 8) || !aligned(gamma, 4) || !aligned(beta, 4) ||
+      !aligned(mean_offset, 4) || !aligned(mean, 4) || !aligned(rstd, 4) ||
+      !aligned(scale, 4) || !aligned(shift, 4) ||
+      (any_running && (!all_running || !aligned(running_mean, 4) || !aligned(running_var, 4) ||
+                       !aligned(num_batches_tracked, 8))) ||
       !(eps >= 0.0) || !(momentum <= 1.0))
     return VEON_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_bn_train_coeffs, dim3(1), dim3(256), 0,
@@ -430,8 +429,8 @@ int veon_bn_bwd_coeffs(const double* stats, const float* gamma, const float* mea
                        const float* rstd, float* ca, float* cb, float* cc, int C,
                        void* stream) {
   if (!bn_channels_ok(C) || !stats || !gamma || !mean || !rstd || !ca || !cb || !cc ||
-      !al8(stats) || !al4(gamma) || !al4(mean) || !al4(rstd) || !al4(ca) || !al4(cb) ||
-      !al4(cc))
+      !aligned(stats, 8) || !aligned(gamma, 4) || !aligned(mean, 4) || !aligned(rstd, 4) ||
+      !aligned(ca, 4) || !aligned(cb, 4) || !aligned(cc, 4))
     return VEON_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_bn_bwd_coeffs, dim3((C + 255) / 256), dim3(256), 0,
                      static_cast<hipStream_t>(stream), stats, gamma, mean, rstd, ca, cb, cc,

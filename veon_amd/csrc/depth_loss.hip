@@ -25,7 +25,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/veon_hip.h"
+#include "host_common.h"
+#include "lane_reduce.h"
 
 namespace {
 constexpr int kWave = 64;
@@ -42,24 +43,6 @@ constexpr float kMinGap = -16.f;               // :420
 enum { R_G = 0, R_ABS = 1, R_BCE = 2, R_FLAGS = 3, R_D = 4, R_T = 5, R_DBCE = 6, R_WIN = 7 };
 // coefficient words (floats)
 enum { C_MEAN = 0, C_A = 1, C_B = 2, C_CE = 3, C_N = 4, C_NFG = 5, C_SQRT = 6, C_CLIPPED = 7 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
 
 // -gamma * |d - c_k|, clamped below at -16 (forward value of the straight-through clamp)
 __device__ __forceinline__ float clamped_gap(float d, float c, float gamma) {
@@ -95,6 +78,7 @@ __global__ __launch_bounds__(kRowBlock) void k_depth_loss_rows(
   }
   float d = best;
   int win = besti;
+  // (arg-min with its index as payload: no shared helper)
 #pragma unroll
   for (int o = kWave / 2; o > 0; o >>= 1) {
     const float ov = __shfl_xor(d, o, kWave);
@@ -116,6 +100,7 @@ __global__ __launch_bounds__(kRowBlock) void k_depth_loss_rows(
     if (v == 0.0f) v = 1e5f;
     t = v < t ? v : t;
   }
+  // (a min by compare and select, as the serial loop above: no shared helper)
 #pragma unroll
   for (int o = kWave / 2; o > 0; o >>= 1) {
     const float ov = __shfl_xor(t, o, kWave);
@@ -136,6 +121,7 @@ __global__ __launch_bounds__(kRowBlock) void k_depth_loss_rows(
     }
     mx = fmaxf(mx, clamped_gap(d, c, gamma));
   }
+  // (arg-max with its index as payload: no shared helper)
 #pragma unroll
   for (int o = kWave / 2; o > 0; o >>= 1) {
     const float ov = __shfl_xor(lbest, o, kWave);
@@ -203,7 +189,7 @@ __global__ __launch_bounds__(kReduceBlock) void k_depth_loss_reduce(
     const float* __restrict__ rec, int64_t rows, float* __restrict__ out,
     float* __restrict__ coef) {
   __shared__ double red[5][kReduceWaves];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid >> 6;
+  const int tid = threadIdx.x;
   const float4* r4 = reinterpret_cast<const float4*>(rec);
 
   double sg = 0.0, sabs = 0.0, sbce = 0.0;
@@ -223,42 +209,24 @@ __global__ __launch_bounds__(kReduceBlock) void k_depth_loss_reduce(
     }
   }
   // the counts as doubles: exact (rows < 2^31)
-  const double w0 = wave_sum(sg), w1 = wave_sum(sabs), w2 = wave_sum(sbce);
-  const double w3 = wave_sum((double)nvalid), w4 = wave_sum((double)nfg);
-  if (lane == 0) {
-    red[0][wv] = w0;
-    red[1][wv] = w1;
-    red[2][wv] = w2;
-    red[3][wv] = w3;
-    red[4][wv] = w4;
-  }
-  __syncthreads();
-  double tg = 0.0, tabs = 0.0, tbce = 0.0, n = 0.0, n_fg = 0.0;
-  for (int i = 0; i < kReduceWaves; ++i) {
-    tg += red[0][i];
-    tabs += red[1][i];
-    tbce += red[2][i];
-    n += red[3][i];
-    n_fg += red[4][i];
-  }
+  double tot[5] = {sg, sabs, sbce, (double)nvalid, (double)nfg};
+  block_sum(tot, red);
+  const double tg = tot[0], tabs = tot[1], tbce = tot[2], n = tot[3], n_fg = tot[4];
   const double mean = tg / n;                  // n = 0: NaN, as the mean of nothing
   __syncthreads();                             // red[] is reused below
 
-  double ss = 0.0;
+  double ss[1] = {0.0};
 #pragma unroll 4
   for (int64_t r = tid; r < rows; r += kReduceBlock) {
     const float4 a = r4[r * 2];
     if (__float_as_int(a.w) & 1) {
       const double dv = (double)a.x - mean;
-      ss += dv * dv;
+      ss[0] += dv * dv;
     }
   }
-  const double v0 = wave_sum(ss);
-  if (lane == 0) red[0][wv] = v0;
-  __syncthreads();
+  block_sum(ss, red);
   if (tid == 0) {
-    double tss = 0.0;
-    for (int i = 0; i < kReduceWaves; ++i) tss += red[0][i];
+    const double tss = ss[0];
     const double var = tss / (n - 1.0);        // n = 1: 0/0 = NaN, as torch.var
     const double Dg = var + 0.15 * mean * mean;
     const double sq = sqrt(Dg);
@@ -303,10 +271,6 @@ __global__ __launch_bounds__(kRowBlock) void k_depth_loss_bwd(
   float* dst = grad + (bn * h * sp + (int64_t)y * sp) * Wp + (int64_t)x * sp;
   for (int i = lane; i < sp * sp; i += kWave)
     dst[(int64_t)(i / sp) * Wp + (i % sp)] = i == win ? r : 0.f;
-}
-
-inline int launch_status() {
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
 }
 
 inline bool scale_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8 || s == 16; }

@@ -14,7 +14,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/veon_hip.h"
+#include "host_common.h"
 
 namespace {
 constexpr int kBlock = 256;
@@ -152,9 +152,6 @@ __global__ __launch_bounds__(kBlock) void k_two_hot_window(
   win[i] = make_int2(k0 | (nk << 16), (int)((unsigned)(k0 + q0) | ((unsigned)nq << 16) | t));
 }
 
-inline int launch_status() {
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
-}
 }  // namespace
 
 extern "C" {

@@ -336,11 +336,7 @@ __global__ __launch_bounds__(256) void k_dual_ln_bwd(
   float* out = part + (int64_t)blockIdx.x * (2 * C + 2 * C2);
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    if (wave > 0) {
-#pragma unroll
-      for (int h = 0; h < NCH; ++h) red[wave - 1][h * 64 + lane] = acc[s][h];
-    }
-    __syncthreads();
+    park_waves<NCH>(acc[s], red, lane, wave);
     if (wave == 0) {
       // sums 0, 1 span the whole row, sums 2, 3 the chunks from q1 on
       float* o = out + (s < 2 ? s * C : 2 * C + (s - 2) * C2);
@@ -348,11 +344,8 @@ __global__ __launch_bounds__(256) void k_dual_ln_bwd(
       for (int h = 0; h < NCH; ++h) {
         const int q = lane + 64 * h;
         if (q >= nchunk || (s >= 2 && q < q1)) continue;
-        float4 t = acc[s][h];
-        add4(&t, red[0][h * 64 + lane]);
-        add4(&t, red[1][h * 64 + lane]);
-        add4(&t, red[2][h * 64 + lane]);
-        reinterpret_cast<float4*>(o)[s < 2 ? q : q - q1] = t;
+        reinterpret_cast<float4*>(o)[s < 2 ? q : q - q1] =
+            add_waves_in_order(acc[s][h], red, h * 64 + lane);
       }
     }
     __syncthreads();

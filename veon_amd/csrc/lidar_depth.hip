@@ -21,7 +21,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/veon_hip.h"
+#include "host_common.h"
 
 namespace {
 constexpr int kBlock = 256;
@@ -74,10 +74,6 @@ __global__ __launch_bounds__(kBlock) void k_lidar_scatter(
     const int ix = (int)x >> bshift, iy = (int)y >> bshift;   // -0.0f -> pixel 0
     atomicMin(out + (bn * Hb + iy) * Wb + ix, __float_as_uint(d));
   }
-}
-
-inline int launch_status() {
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
 }
 
 inline int block_shift(int block) {

@@ -48,15 +48,10 @@ __global__ __launch_bounds__(256) void k_rows_colsum(const bf16_t* __restrict__ 
 #pragma unroll
       for (int k = 0; k < 8; ++k) acc[k] += bf2f((bf16_t)c[k]);
     }
-  if (wave > 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) red[wave - 1][k * 64 + lane] = acc[k];
-  }
-  __syncthreads();
+  park_waves<8>(acc, red, lane, wave);
   if (wave == 0 && has) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
-      acc[k] = ((acc[k] + red[0][k * 64 + lane]) + red[1][k * 64 + lane]) + red[2][k * 64 + lane];
+    for (int k = 0; k < 8; ++k) acc[k] = add_waves_in_order(acc[k], red, k * 64 + lane);
     float* q = part + (int64_t)blockIdx.y * N + chunk * 8;
     *reinterpret_cast<float4*>(q) = float4{acc[0], acc[1], acc[2], acc[3]};
     *reinterpret_cast<float4*>(q + 4) = float4{acc[4], acc[5], acc[6], acc[7]};
@@ -168,15 +163,10 @@ __global__ __launch_bounds__(256) void k_layernorm_f32_bwd(
       *reinterpret_cast<float4*>(q + 4) = float4{a[4], a[5], a[6], a[7]};
     }
   }
-  if (wave > 0) {
-#pragma unroll
-    for (int k = 0; k < 2 * E; ++k) red[wave - 1][k * 64 + lane] = acc[k];
-  }
-  __syncthreads();
+  park_waves<2 * E>(acc, red, lane, wave);
   if (wave == 0) {
 #pragma unroll
-    for (int k = 0; k < 2 * E; ++k)
-      acc[k] = ((acc[k] + red[0][k * 64 + lane]) + red[1][k * 64 + lane]) + red[2][k * 64 + lane];
+    for (int k = 0; k < 2 * E; ++k) acc[k] = add_waves_in_order(acc[k], red, k * 64 + lane);
     float* o = part + (int64_t)blockIdx.x * 2 * C;
 #pragma unroll
     for (int s = 0; s < 2; ++s)

@@ -1,8 +1,10 @@
 // What the LayerNorm / GELU training passes share (conv2d_train.hip on padded half images,
 // linear_train.hip on token rows): GELU with its slope, the lane layout of a row of up to
 // 1024 channels with its statistics, and the fixed-order second stage of the per-channel
-// sums.  Included inside each file's translation unit after mfma_common.h.
+// sums.  The lane and wave sums themselves (wave_sum, add_waves_in_order) are in
+// lane_reduce.h.
 #pragma once
+#include "lane_reduce.h"
 #include "mfma_common.h"
 
 namespace {
@@ -37,12 +39,6 @@ __device__ __forceinline__ void gelu_and_slope(float y, float* g, float* dg) {
   q = fmaf(q, t, 8.681167662e-02f);
   const float hs = (q * t) * e;
   *dg = fmaf(y * 0.39894228040143268f, e, y > 0.f ? 1.f - hs : hs);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
 }
 
 // A lane holds N (1: C <= 512, 2: C <= 1024) 16-byte chunks of a padded row: channels

@@ -29,7 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/veon_hip.h"
+#include "host_common.h"
 
 namespace {
 
@@ -540,10 +540,6 @@ __global__ __launch_bounds__(kBlock) void k_rank_in_bin(
     const int j = k - (wx & 0xffff);
     ranks_depth[slot] = pix * K + ((unsigned)j < (unsigned)(wx >> 16) ? 1 + j : 0);
   }
-}
-
-inline int launch_status() {
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
 }
 
 struct Workspace {

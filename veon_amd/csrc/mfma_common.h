@@ -1,4 +1,6 @@
-// Shared typedefs / helpers of the MFMA kernels (vit_block.hip, conv3d.hip).
+// Shared typedefs / helpers of the MFMA kernels (vit_block.hip, conv3d.hip and the
+// training passes).  The host helpers of their entry points (launch_status, aligned)
+// come with it from host_common.h.
 // Fragment convention for v_mfma_f32_16x16x32_bf16 (guide section 3): lane l
 // holds A[row l&15][k = 8(l>>4)+j] and B[k = 8(l>>4)+j][col l&15], j = 0..7;
 // D[row 4(l>>4)+reg][col l&15].
@@ -6,7 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/veon_hip.h"
+#include "host_common.h"
 
 namespace {
 
@@ -125,10 +127,7 @@ __device__ __forceinline__ float gelu_erf(float x) {
   const float e = __builtin_amdgcn_exp2f(ax * ax * -0.72134752044448170f);
   return fmaxf(x, 0.f) - ax * (p * t) * e;
 }
-inline int launch_status() {
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
-}
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool al16(const void* p) { return aligned(p, 16); }
 
 constexpr int kNumCU = 256;  // MI355X
 

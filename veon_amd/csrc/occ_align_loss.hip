@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lane_reduce.h"
 #include "mfma_common.h"
 #include "occ_interp.h"
 
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(64) void k_table_norms(const float* __restrict__ ta
   const float* e = table + (int64_t)blockIdx.x * C;
   float s = 0.f;
   for (int c = threadIdx.x; c < C; c += 64) s += e[c] * e[c];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  s = wave_sum(s);
   if (threadIdx.x == 0) norms[blockIdx.x] = fmaxf(sqrtf(s), eps);
 }
 
@@ -114,8 +115,8 @@ __global__ __launch_bounds__(256) void k_align_fwd(
     }
     return;
   }
-  const Axis az = source(z, g.scz, g.zi), ay = source(y, g.scy, g.yi),
-             ax = source(x, g.scx, g.xi);
+  const Axis az = source_clamped(z, g.scz, g.zi), ay = source_clamped(y, g.scy, g.yi),
+             ax = source_clamped(x, g.scx, g.xi);
   float f[K][W];
   blend_rows<W, K>(feat, fs, C, lane, az, ay, ax, f);
 
@@ -175,8 +176,8 @@ __global__ __launch_bounds__(256) void k_align_rows(
     ok = x >= 0 && x < g.Xo && y >= 0 && y < g.Yo && z >= 0 && z < g.Zo;
   }
   if (ok) {
-    const Axis az = source(z, g.scz, g.zi), ay = source(y, g.scy, g.yi),
-               ax = source(x, g.scx, g.xi);
+    const Axis az = source_clamped(z, g.scz, g.zi), ay = source_clamped(y, g.scy, g.yi),
+               ax = source_clamped(x, g.scx, g.xi);
     float f[K][W];
     blend_rows<W, K>(feat, fs, C, lane, az, ay, ax, f);
     for (int e = e0; e < e1; ++e) {
@@ -271,10 +272,6 @@ __global__ __launch_bounds__(256) void k_align_gather(
   }
 }
 
-inline bool aligned(const void* p, unsigned a) {
-  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
-}
-
 inline unsigned groups(int64_t n) { return (unsigned)((n + kPerWG - 1) / kPerWG); }
 
 // chunks of 32 * W channels that hold C: the instantiated counts
@@ -325,7 +322,7 @@ bool common_args(const float* feat, const int64_t* st, int C, int B, int zi, int
   if (st[0] < 0 || st[1] <= 0 || st[2] < 0 || st[3] < 0 || st[4] < 0) return false;
   // channels-last rows: C may not run past the row into the next voxel
   if (st[1] == 1 && xi > 1 && C > st[4]) return false;
-  out->fs = Strides5{st[0], st[1], st[2], st[3], st[4]};
+  out->fs = strides5(st);
   out->g = Grid{zi, yi, xi, Zo, Yo, Xo, (float)zi / (float)Zo, (float)yi / (float)Yo,
                 (float)xi / (float)Xo};
   out->fb = feat + batch * st[0];

@@ -44,10 +44,6 @@ struct Geom {
   float dlo, dhi;
 };
 
-inline bool aligned(const void* p, uintptr_t a) {
-  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
-}
-
 // Voxel centre -> (u, v, depth) in the augmented image, the mirror's operation sequence:
 // the 3 x 4 affine, x and y over z, the full 3 x 3 post rotation plus the translation.
 // -> the six in-view comparisons (false for NaN, as in torch).

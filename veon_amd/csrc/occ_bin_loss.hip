@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lane_reduce.h"
 #include "mfma_common.h"
 #include "occ_interp.h"
 
@@ -30,38 +31,14 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Sum over the workgroup in a fixed order (shuffle tree, then the waves in order); the
-// result is valid in thread 0.
-__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[kWaves]) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[0][wv] = a;
-    red[1][wv] = b;
-  }
-  __syncthreads();
-  a = 0.0;
-  b = 0.0;
-  for (int i = 0; i < kWaves; ++i) {
-    a += red[0][i];
-    b += red[1][i];
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void k_bin_fwd(
     const float* __restrict__ logits, Strides5 ls, Grid g, int64_t total,
     const unsigned char* __restrict__ labels, const float* __restrict__ cw, int ignore_index,
     int free_index, float* __restrict__ coef, double* __restrict__ partials) {
   __shared__ double red[2][kWaves];
   const int64_t n = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  double num = 0.0, den = 0.0;
+  double sums[2] = {0.0, 0.0};   // numerator, denominator
+  double &num = sums[0], &den = sums[1];
   if (n < total) {
     const int zo = (int)(n % g.Zo);
     const int yo = (int)((n / g.Zo) % g.Yo);
@@ -70,8 +47,8 @@ __global__ __launch_bounds__(kBlock) void k_bin_fwd(
     const int lab = labels[n];
     float c = 0.f;
     if (lab != ignore_index) {
-      const Axis az = source(zo, g.scz, g.zi), ay = source(yo, g.scy, g.yi),
-                 ax = source(xo, g.scx, g.xi);
+      const Axis az = source_clamped(zo, g.scz, g.zi), ay = source_clamped(yo, g.scy, g.yi),
+                 ax = source_clamped(xo, g.scx, g.xi);
       int64_t off[8];
       corner_offsets(off, ls, az, ay, ax);
       const float* l0 = logits + b * ls.b;
@@ -95,7 +72,7 @@ __global__ __launch_bounds__(kBlock) void k_bin_fwd(
     }
     coef[n] = c;
   }
-  block_sum2(num, den, red);
+  block_sum(sums, red);
   if (threadIdx.x == 0) {
     partials[2 * (int64_t)blockIdx.x] = num;
     partials[2 * (int64_t)blockIdx.x + 1] = den;
@@ -105,12 +82,13 @@ __global__ __launch_bounds__(kBlock) void k_bin_fwd(
 __global__ __launch_bounds__(kBlock) void k_bin_reduce(const double* __restrict__ partials,
                                                       int64_t count, float* __restrict__ out) {
   __shared__ double red[2][kWaves];
-  double num = 0.0, den = 0.0;
+  double sums[2] = {0.0, 0.0};   // numerator, denominator
+  double &num = sums[0], &den = sums[1];
   for (int64_t i = threadIdx.x; i < count; i += kBlock) {
     num += partials[2 * i];
     den += partials[2 * i + 1];
   }
-  block_sum2(num, den, red);
+  block_sum(sums, red);
   if (threadIdx.x == 0) {
     out[0] = (float)(num / den);                 // nothing counted: 0/0 = NaN, as torch
     out[1] = den > 0.0 ? (float)(1.0 / den) : 0.f;  // ... with an all-zero gradient
@@ -159,10 +137,6 @@ __global__ __launch_bounds__(kBlock) void k_bin_bwd(
   grad[(b * 2 + 1) * plane + at] = -v;
 }
 
-inline bool al(const void* p, unsigned a) {
-  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
-}
-
 // output voxels of (B, Zo, Yo, Xo), or -1 when a 1-D grid of 256-thread workgroups and
 // 32-bit axis indices cannot cover them
 inline int64_t out_voxels(int B, int Zo, int Yo, int Xo) {
@@ -191,14 +165,15 @@ extern "C" int veon_occ_bin_loss_fwd(const float* logits, const int64_t* logit_s
   const int64_t total = out_voxels(B, Zo, Yo, Xo);
   const int64_t st_ok = logit_strides ? 1 : 0;
   if (total < 0 || !st_ok || zi <= 0 || yi <= 0 || xi <= 0 || !logits || !labels ||
-      !class_weights || !coef || !workspace || !out || !al(logits, 4) ||
-      !al(class_weights, 4) || !al(coef, 4) || !al(out, 4) || !al(workspace, 8))
+      !class_weights || !coef || !workspace || !out || !aligned(logits, 4) ||
+      !aligned(class_weights, 4) || !aligned(coef, 4) || !aligned(out, 4) ||
+      !aligned(workspace, 8))
     return VEON_ERR_BAD_ARG;
   const int64_t* st = logit_strides;
   if (st[0] < 0 || st[1] < 0 || st[2] < 0 || st[3] < 0 || st[4] < 0) return VEON_ERR_BAD_ARG;
   if (workspace_bytes < veon_occ_bin_loss_workspace_bytes(B, Zo, Yo, Xo))
     return VEON_ERR_WORKSPACE;
-  const Strides5 ls{st[0], st[1], st[2], st[3], st[4]};
+  const Strides5 ls = strides5(st);
   const Grid g{zi, yi, xi, Zo, Yo, Xo, (float)zi / (float)Zo, (float)yi / (float)Yo,
                (float)xi / (float)Xo};
   const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -216,7 +191,7 @@ extern "C" int veon_occ_bin_loss_bwd(const float* coef, const float* out, const 
   if (zi <= 0 || yi <= 0 || xi <= 0 || zi > (1 << 20) || yi > (1 << 20) || xi > (1 << 20))
     return VEON_ERR_BAD_ARG;
   if (out_voxels(B, 2 * zi, 2 * yi, 2 * xi) < 0 || !coef || !out || !gout || !grad ||
-      !al(coef, 4) || !al(out, 4) || !al(gout, 4) || !al(grad, 4))
+      !aligned(coef, 4) || !aligned(out, 4) || !aligned(gout, 4) || !aligned(grad, 4))
     return VEON_ERR_BAD_ARG;
   const Grid g{zi, yi, xi, 2 * zi, 2 * yi, 2 * xi, 0.5f, 0.5f, 0.5f};
   const int64_t nlow = (int64_t)B * zi * yi * xi;

@@ -3,7 +3,7 @@
 // same confusion matrix for label volumes that already exist.
 //
 // k_occ_labels computes what k_occ_classify (occ_head.hip) computes per voxel -- the
-// same source indices, corner offsets, blend nest and class loop (occ_tail.h), so the
+// same source indices, corner offsets, blend nest and class loop (occ_interp.h), so the
 // same label bit for bit -- and writes NOTHING but the uint8 label volume (B,Xo,Yo,Zo)
 // that VEONTemporal.simple_test returns (detectors/veon_temporal.py:219-241): 640 KB
 // at the VEON shape instead of 48 MB of upsampled logits and 5 MB of int64 labels.
@@ -25,8 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "occ_tail.h"
-#include "veon_hip.h"
+#include "occ_interp.h"
+#include "host_common.h"
 
 namespace {
 
@@ -60,21 +60,21 @@ __device__ __forceinline__ int label_of(const float* __restrict__ sem, const Str
   int cls = 0;
   bool bad = false;
   const float* sp = sem + b * ss.b;
-  const Corners ks = corners(ss, az, ay, ax);
+  int ks[8];
+  corner_offsets(ks, ss, az, ay, ax);
   if (VEC4) {
 #pragma unroll 1
     for (int c = 0; c < Q; c += 4) {
       float4 k4[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) k4[q] = *reinterpret_cast<const float4*>(sp + c + ks.o[q]);
+      for (int q = 0; q < 8; ++q) k4[q] = *reinterpret_cast<const float4*>(sp + c + ks[q]);
       float val4[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        auto at = [&](int q) { return reinterpret_cast<const float*>(&k4[q])[e]; };
-        val4[e] = az.l0 * (ay.l0 * (ax.l0 * at(0) + ax.l1 * at(1)) +
-                           ay.l1 * (ax.l0 * at(2) + ax.l1 * at(3))) +
-                  az.l1 * (ay.l0 * (ax.l0 * at(4) + ax.l1 * at(5)) +
-                           ay.l1 * (ax.l0 * at(6) + ax.l1 * at(7)));
+        float k8[8];   // channel c + e of the eight corners
+#pragma unroll
+        for (int q = 0; q < 8; ++q) k8[q] = reinterpret_cast<const float*>(&k4[q])[e];
+        val4[e] = blend(k8, az, ay, ax);
       }
       // Every value is needed here, also those of the surplus floats past class Q - 1:
       // without the stores of k_occ_classify the compiler otherwise computes them under
@@ -106,7 +106,8 @@ __device__ __forceinline__ int label_of(const float* __restrict__ sem, const Str
   }
   const bool scored = !bad && vmax < INFINITY && vmax > -INFINITY;
   const float* bp = bin + b * bs.b;
-  const Corners kb = corners(bs, az, ay, ax);
+  int kb[8];
+  corner_offsets(kb, bs, az, ay, ax);
   const float o0 = blend(bp, kb, az, ay, ax), o1 = blend(bp + bs.c, kb, az, ay, ax);
   const float om = o0 > o1 ? o0 : o1;
   const float e0 = expf(o0 - om), e1 = expf(o1 - om);
@@ -244,14 +245,6 @@ __global__ __launch_bounds__(THREADS) void k_confusion(
   flush_counters(cnt, n_cl, hist);
 }
 
-inline int launch_status() {
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
-}
-
-inline bool aligned(const void* p, int w) {
-  return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(w - 1)) == 0;
-}
-
 template <bool VEC4>
 void launch_labels(int W, int blocks, size_t lds, hipStream_t st, const float* sem,
                    const Strides5& ss, int Q, const float* bin, const Strides5& bs, int B,
@@ -287,10 +280,7 @@ extern "C" int veon_occ_labels(const float* sem, const int64_t* sem_strides, int
   if (total > 0x7fffffffLL) return VEON_ERR_BAD_ARG;
   if (!strides_fit(sem_strides, zi, yi, xi) || !strides_fit(bin_strides, zi, yi, xi))
     return VEON_ERR_BAD_ARG;
-  const Strides5 ss{sem_strides[0], sem_strides[1], sem_strides[2], sem_strides[3],
-                    sem_strides[4]};
-  const Strides5 bs{bin_strides[0], bin_strides[1], bin_strides[2], bin_strides[3],
-                    bin_strides[4]};
+  const Strides5 ss = strides5(sem_strides), bs = strides5(bin_strides);
   // ATen: scale = in / out in float (area_pixel_compute_scale, no scale_factor given)
   const Geometry g{zi, yi, xi, Zo, Yo, Xo, (float)zi / (float)Zo, (float)yi / (float)Yo,
                    (float)xi / (float)Xo};
@@ -307,8 +297,7 @@ extern "C" int veon_occ_labels(const float* sem, const int64_t* sem_strides, int
     }
   }
   const int64_t tiles = (int64_t)B * ((Yo + TY - 1) / TY) * ((Xo + TX - 1) / TX);
-  const int64_t rounds = (tiles + MAX_BLOCKS - 1) / MAX_BLOCKS;
-  const int blocks = (int)((tiles + rounds - 1) / rounds);   // even shares, <= MAX_BLOCKS
+  const int blocks = even_share_blocks(tiles, MAX_BLOCKS);
   const size_t lds = (size_t)((TX * TY * Zo + 15) & ~15) +
                      (hist ? sizeof(unsigned) * (Q + 1) * (Q + 1) : 0);
   const hipStream_t st = static_cast<hipStream_t>(stream);

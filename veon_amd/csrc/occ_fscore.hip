@@ -31,7 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "veon_hip.h"
+#include "host_common.h"
 
 namespace {
 
@@ -159,6 +159,7 @@ __global__ __launch_bounds__(THREADS) void k_occ_fscore(
         }
       c[3] = (unsigned)__popcll(own.y & near);
     }
+    // (integer counts by __shfl_down into lane 0 and red[wave][k]: not block_sum's layout)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
 #pragma unroll
@@ -176,10 +177,6 @@ __global__ __launch_bounds__(THREADS) void k_occ_fscore(
       if (sum) atomicAdd(counts + (int64_t)b * 4 + tid, (unsigned long long)sum);
     }
   }
-}
-
-inline bool aligned(const void* p, int w) {
-  return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(w - 1)) == 0;
 }
 
 // (2r + 1)^2 reaches in [-1, 63] from a host array into the kernel's table
@@ -237,13 +234,12 @@ extern "C" int veon_occ_fscore_counts(const void* pred, int pred_elem_bytes,
     }
   }
   const int64_t tiles = (int64_t)B * ((X + T - 1) / T) * ((Y + T - 1) / T);
-  const int64_t rounds = (tiles + MAX_BLOCKS - 1) / MAX_BLOCKS;
-  const int blocks = (int)((tiles + rounds - 1) / rounds);   // even shares, <= MAX_BLOCKS
+  const int blocks = even_share_blocks(tiles, MAX_BLOCKS);
   const hipStream_t st = static_cast<hipStream_t>(stream);
   unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
   if (pred_elem_bytes == 1)
     launch<uint8_t>(W, blocks, st, pred, gt, mask, B, X, Y, Z, tab, c);
   else
     launch<int64_t>(W, blocks, st, pred, gt, mask, B, X, Y, Z, tab, c);
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
+  return launch_status();
 }

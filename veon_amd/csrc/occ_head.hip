@@ -19,8 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "occ_tail.h"
-#include "veon_hip.h"
+#include "occ_interp.h"
+#include "host_common.h"
 
 namespace {
 
@@ -56,21 +56,21 @@ __global__ __launch_bounds__(256) void k_occ_classify(
   bool bad = false;
   const float* sp = sem + b * ss.b;
   float* so = sem_out + (int64_t)b * Q * plane + v;
-  const Corners ks = corners(ss, az, ay, ax);
+  int ks[8];
+  corner_offsets(ks, ss, az, ay, ax);
   if (VEC4) {
 #pragma unroll 1
     for (int c = 0; c < Q; c += 4) {
       float4 k4[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) k4[q] = *reinterpret_cast<const float4*>(sp + c + ks.o[q]);
+      for (int q = 0; q < 8; ++q) k4[q] = *reinterpret_cast<const float4*>(sp + c + ks[q]);
       float val4[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        auto at = [&](int q) { return reinterpret_cast<const float*>(&k4[q])[e]; };
-        val4[e] = az.l0 * (ay.l0 * (ax.l0 * at(0) + ax.l1 * at(1)) +
-                           ay.l1 * (ax.l0 * at(2) + ax.l1 * at(3))) +
-                  az.l1 * (ay.l0 * (ax.l0 * at(4) + ax.l1 * at(5)) +
-                           ay.l1 * (ax.l0 * at(6) + ax.l1 * at(7)));
+        float k8[8];   // channel c + e of the eight corners
+#pragma unroll
+        for (int q = 0; q < 8; ++q) k8[q] = reinterpret_cast<const float*>(&k4[q])[e];
+        val4[e] = blend(k8, az, ay, ax);
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -99,7 +99,8 @@ __global__ __launch_bounds__(256) void k_occ_classify(
   }
   const bool scored = !bad && vmax < INFINITY && vmax > -INFINITY;
   const float* bp = bin + b * bs.b;
-  const Corners kb = corners(bs, az, ay, ax);
+  int kb[8];
+  corner_offsets(kb, bs, az, ay, ax);
   const float o0 = blend(bp, kb, az, ay, ax), o1 = blend(bp + bs.c, kb, az, ay, ax);
   bin_out[((int64_t)b * 2 + 0) * plane + v] = o0;
   bin_out[((int64_t)b * 2 + 1) * plane + v] = o1;
@@ -107,10 +108,6 @@ __global__ __launch_bounds__(256) void k_occ_classify(
   const float e0 = expf(o0 - om), e1 = expf(o1 - om);
   const bool keep = scored && (e0 / (e0 + e1) > 0.5f);
   cls_out[(((int64_t)b * Xo + x) * Yo + y) * Zo + z] = keep ? cls : Q;
-}
-
-inline int launch_status() {
-  return hipGetLastError() == hipSuccess ? VEON_OK : VEON_ERR_LAUNCH;
 }
 
 }  // namespace
@@ -129,10 +126,7 @@ extern "C" int veon_occ_classify(const float* sem, const int64_t* sem_strides, i
   if (total > 0x7fffffffLL) return VEON_ERR_BAD_ARG;
   if (!strides_fit(sem_strides, zi, yi, xi) || !strides_fit(bin_strides, zi, yi, xi))
     return VEON_ERR_BAD_ARG;
-  const Strides5 ss{sem_strides[0], sem_strides[1], sem_strides[2], sem_strides[3],
-                    sem_strides[4]};
-  const Strides5 bs{bin_strides[0], bin_strides[1], bin_strides[2], bin_strides[3],
-                    bin_strides[4]};
+  const Strides5 ss = strides5(sem_strides), bs = strides5(bin_strides);
   // ATen: scale = in / out in float (area_pixel_compute_scale, no scale_factor given)
   const float scz = (float)zi / (float)Zo, scy = (float)yi / (float)Yo,
               scx = (float)xi / (float)Xo;

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lane_reduce.h"
 #include "mfma_common.h"
 #include "occ_interp.h"
 
@@ -42,6 +43,8 @@ __global__ __launch_bounds__(64) void k_prompt_norms(const float* __restrict__ e
   const float* e = emb + (int64_t)blockIdx.x * C;
   float s = 0.f;
   for (int c = threadIdx.x; c < C; c += 64) s += e[c] * e[c];
+  // written out: through wave_sum (lane_reduce.h) the compiler schedules this kernel
+  // differently, and the file is on the benchmark's path
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
   if (threadIdx.x == 0) norms[blockIdx.x] = fmaxf(sqrtf(s), 1e-8f);
 }
@@ -66,8 +69,8 @@ __global__ __launch_bounds__(256) void k_occ_retrieve(
     }
     return;
   }
-  const Axis az = source(z, g.scz, g.zi), ay = source(y, g.scy, g.yi),
-             ax = source(x, g.scx, g.xi);
+  const Axis az = source_clamped(z, g.scz, g.zi), ay = source_clamped(y, g.scy, g.yi),
+             ax = source_clamped(x, g.scx, g.xi);
   int64_t off[8];
   corner_offsets(off, fs, az, ay, ax);
 
@@ -171,10 +174,6 @@ void launch_scalar(const T* feat, const Strides5& fs, int C, const float* bin,
                                      bin_prob, st);
 }
 
-inline bool aligned(const void* p, unsigned a) {
-  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
-}
-
 }  // namespace
 
 extern "C" int veon_occ_retrieve(const void* feat, int feat_is_half,
@@ -202,12 +201,11 @@ extern "C" int veon_occ_retrieve(const void* feat, int feat_is_half,
   if (P == 0) return VEON_OK;
   const hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_prompt_norms, dim3((unsigned)Q), dim3(64), 0, s, emb, C, emb_norms);
-  const Strides5 fs{st[0], st[1], st[2], st[3], st[4]};
+  const Strides5 fs = strides5(st);
   Strides5 bs{0, 0, 0, 0, 0};
   const float* bin_b = nullptr;
   if (bin_prob) {
-    bs = Strides5{bin_strides[0], bin_strides[1], bin_strides[2], bin_strides[3],
-                  bin_strides[4]};
+    bs = strides5(bin_strides);
     bin_b = bin + batch * bs.b;
   }
   const Grid g{zi, yi, xi, Zo, Yo, Xo, (float)zi / (float)Zo, (float)yi / (float)Yo,

@@ -92,6 +92,7 @@ __global__ __launch_bounds__(256) void k_deform_attn(
     float part = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) part = fmaf(qv[k], samp[k], part);
+    // (KL-split sum, 1 up to KL / 2: its own order, written out)
 #pragma unroll
     for (int d = 1; d < KL; d <<= 1) part += __shfl_xor(part, d);
     const float other = __shfl_xor(part, KL);

@@ -108,6 +108,7 @@ __global__ __launch_bounds__(256) void k_deform_attn_bwd(
     gx = (p.fx > 0.f && p.fx < (float)(X - 1)) ? gx * jx * (1.f - p.o0 * p.o0) : 0.f;
     gy = (p.fy > 0.f && p.fy < (float)(Y - 1)) ? gy * jy * (1.f - p.o1 * p.o1) : 0.f;
     gz = (p.fz > 0.f && p.fz < (float)(Z - 1)) ? gz * jz * (1.f - p.o2 * p.o2) : 0.f;
+    // (KL-split sums of four values in step, 1 up to KL / 2: written out)
 #pragma unroll
     for (int d = 1; d < KL; d <<= 1) {
       part += __shfl_xor(part, d);
@@ -234,6 +235,7 @@ __global__ __launch_bounds__(256) void k_deform_attn_bwd_dkv(
   }
   const int n = max(zhi - zlo + 1, 0) * max(yhi - ylo + 1, 0) * max(xhi - xlo + 1, 0);
   int nmax = n;                    // the wave walks its longest box
+  // (a max over a run-time lane stride: no shared helper)
   for (int d = lpv; d < 64; d <<= 1) nmax = max(nmax, __shfl_xor(nmax, d));
 
   const int64_t plane0 = (int64_t)b * Zp;
@@ -256,6 +258,7 @@ __global__ __launch_bounds__(256) void k_deform_attn_bwd_dkv(
     const float w = wz * wy * wx;
     const float2 rc = rec[(sv * heads + h) * S + s];
     float ck = on ? w * rc.x : 0.f, cv = on ? w * rc.y : 0.f;
+    // (S-split sums of two values in step, 1 up to S / 2: written out)
 #pragma unroll
     for (int d = 1; d < S; d <<= 1) {
       ck += __shfl_xor(ck, d);

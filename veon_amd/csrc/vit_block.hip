@@ -51,6 +51,7 @@ __global__ __launch_bounds__(256) void k_layernorm(
       s += v[i];
     }
   }
+  // (written out, not wave_sum of lane_reduce.h: the call changes this kernel's code)
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
   const float mean = s / (float)d;
   float q = 0.f;
@@ -96,6 +97,7 @@ __global__ __launch_bounds__(256) void k_layernorm_padded(
       s += v[i];
     }
   }
+  // (written out, not wave_sum of lane_reduce.h: the call changes this kernel's code)
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
   const float mean = s / (float)d;
   float q = 0.f;
@@ -140,6 +142,7 @@ __global__ __launch_bounds__(256) void k_layernorm_v4(
     v[i] = xr[i * 64 + lane];
     s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
   }
+  // (written out, not wave_sum of lane_reduce.h: the call changes this kernel's code)
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
   const float mean = s / (float)d;
   float q = 0.f;
@@ -906,6 +909,7 @@ __global__ __launch_bounds__(256) void k_layernorm_f32(
     }
     s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
   }
+  // (written out: a half wave per row, 16 down to 1; a shared helper changes the code)
 #pragma unroll
   for (int d = 16; d >= 1; d >>= 1) s += __shfl_xor(s, d);
   const float mean = s / D;
@@ -954,6 +958,7 @@ __global__ __launch_bounds__(256) void k_layernorm_f32_d64(
   if (row >= T) return;  // a whole quarter-wave leaves; the shuffles stay inside one
   const float4 v = reinterpret_cast<const float4*>(x + row * 64)[l];
   float s = (v.x + v.y) + (v.z + v.w);
+  // (written out: a quarter wave per row, 8 down to 1; a shared helper changes the code)
 #pragma unroll
   for (int d = 8; d >= 1; d >>= 1) s += __shfl_xor(s, d);
   const float mean = s / 64;

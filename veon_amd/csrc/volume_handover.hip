@@ -92,10 +92,6 @@ __global__ __launch_bounds__(256) void k_sigm_bwd_pack_cl(
   *reinterpret_cast<uint2*>(out + srow * C + c) = q;
 }
 
-inline bool al(const void* p, unsigned a) {
-  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
-}
-
 // rows of the padded grid, or -1 when the sizes are not supported
 inline int64_t padded_rows(int B, int Z, int Y, int X) {
   if (B <= 0 || Z <= 0 || Y <= 0 || X <= 0 || Z > (1 << 20) || Y > (1 << 20) || X > (1 << 20))
@@ -112,8 +108,8 @@ inline int64_t padded_rows(int B, int Z, int Y, int X) {
 extern "C" int veon_volume_unpack_cl_f32(const void* padded, float* out, int B, int Cp, int C,
                                          int Z, int Y, int X, void* stream) {
   const int64_t M = padded_rows(B, Z, Y, X);
-  if (M < 0 || !padded || !out || C <= 0 || C > Cp || Cp % 4 != 0 || !al(padded, 8) ||
-      !al(out, 16))
+  if (M < 0 || !padded || !out || C <= 0 || C > Cp || Cp % 4 != 0 || !aligned(padded, 8) ||
+      !aligned(out, 16))
     return VEON_ERR_BAD_ARG;
   const int64_t total = (int64_t)B * Z * Y * X * ((C + 3) / 4);
   const int64_t blocks = (total + 255) / 256;
@@ -130,15 +126,15 @@ extern "C" int veon_volume_sigm_bwd_pack_cl(const float* grad, const int64_t* gr
                                             int X, void* stream) {
   const int64_t M = padded_rows(B, Z, Y, X);
   if (M < 0 || !grad || !grad_strides || !f_storage || !out_storage || f_storage == out_storage ||
-      C <= 0 || C % 4 != 0 || guard_rows != veon_conv3d_guard_rows(Y, X) || !al(grad, 4) ||
-      !al(f_storage, 8) || !al(out_storage, 8))
+      C <= 0 || C % 4 != 0 || guard_rows != veon_conv3d_guard_rows(Y, X) || !aligned(grad, 4) ||
+      !aligned(f_storage, 8) || !aligned(out_storage, 8))
     return VEON_ERR_BAD_ARG;
   const int64_t* st = grad_strides;
   if (st[0] < 0 || st[1] < 0 || st[2] < 0 || st[3] < 0) return VEON_ERR_BAD_ARG;
   // channels-last rows: C may not run past the row into the next voxel
   if (X > 1 && C > st[3]) return VEON_ERR_BAD_ARG;
   const Strides4 gs{st[0], st[1], st[2], st[3]};
-  const int vec = al(grad, 16) && st[0] % 4 == 0 && st[1] % 4 == 0 && st[2] % 4 == 0 &&
+  const int vec = aligned(grad, 16) && st[0] % 4 == 0 && st[1] % 4 == 0 && st[2] % 4 == 0 &&
                   st[3] % 4 == 0;
   const int64_t total = (M + 2 * guard_rows) * (C / 4);
   const int64_t blocks = (total + 255) / 256;

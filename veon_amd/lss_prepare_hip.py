@@ -9,8 +9,6 @@ from . import _lib, lss_prepare
 from .ops.bev_pool_v2 import bev_pool as _bp
 from .ops.bev_pool_v2.bev_pool import mark_sorted
 
-_F3 = ctypes.c_float * 3
-
 
 def _axes(frustum, device):
     """Device copies of the frustum axes xs[W], ys[H], ds[D], cached on the
@@ -141,9 +139,8 @@ def clear_workspaces(owner=None):
 
 
 def _grid_host(lower, interval, gsize):
-    return (_F3(*[float(v) for v in lower.tolist()]),
-            _F3(*[float(v) for v in interval.tolist()]),
-            _F3(*[float(v) for v in gsize.tolist()]))
+    return tuple(_lib.host_array([float(v) for v in t.tolist()], ctypes.c_float)
+                 for t in (lower, interval, gsize))
 
 
 def _vpb(gsize):
@@ -180,8 +177,7 @@ def prepare_device(dims, coor, geometry, lower, interval, gsize, device):
         frustum, pri, pt, cb, tr, bd = geometry
         geo = list(_axes(frustum, device)) + [_f32c(t) for t in (pri, pt, cb, tr, bd)]
     _lib.launch('veon_lss_prepare', device, B, N, D, H, W, coor, *geo,
-                ctypes.cast(glo, ctypes.c_void_p), ctypes.cast(gstep, ctypes.c_void_p),
-                ctypes.cast(gsz, ctypes.c_void_p), vpb, ws, ws_bytes, out.ranks_bev,
+                glo, gstep, gsz, vpb, ws, ws_bytes, out.ranks_bev,
                 out.ranks_depth, out.ranks_feat, out.interval_starts, out.interval_lengths,
                 out.plan, out.counts)
     return out
@@ -204,8 +200,7 @@ def prepare_cameras(frustum, sensor2ego, cam2imgs, post_rots, post_trans, bda, l
                                               bda))
     glo, gstep, gsz = _grid_host(lower, interval, gsize)
     args = (B, N, D, H, W, xs, ys, ds, s2e, k, pr, pt, bd,
-            ctypes.cast(glo, ctypes.c_void_p), ctypes.cast(gstep, ctypes.c_void_p),
-            ctypes.cast(gsz, ctypes.c_void_p), vpb, ws.ws, ws.ws_bytes,
+            glo, gstep, gsz, vpb, ws.ws, ws.ws_bytes,
             0 if ws.dirty else 1,   # hist_is_zero
             ws.ranks_bev, ws.ranks_depth, ws.ranks_feat, ws.interval_starts,
             ws.interval_lengths, ws.plan, ws.vstart, ws.counts)

@@ -10,8 +10,6 @@ read back, and the pair can sit in a captured graph.  ``bin_occ_loss_torch`` is 
 sequence at any dtype (the CPU path and the tests' yardstick); ``bin_occ_loss_bwd_ref``
 restates the native backward's gather formulation in torch, so the algorithm is checked
 without a device."""
-import ctypes
-
 import torch
 import torch.nn.functional as F
 
@@ -104,10 +102,6 @@ def bin_occ_loss_bwd_ref(bin_low, labels, class_weights, occ_size, ignore_index=
 
 
 # ------------------------------------------------------------------ native path
-def _strides(t):
-    return ctypes.cast((ctypes.c_int64 * 5)(*t.stride()), ctypes.c_void_p)
-
-
 # (B, Z, Y, X, device) -> fp64 partial sums, consumed inside one call.  As with the other
 # native caches, one buffer per shape and device serves every stream: two streams that run
 # the loss at the same shape concurrently must be ordered by the caller.
@@ -137,7 +131,7 @@ def loss_forward(bin_low, labels, class_weights, occ_size, ignore_index=255, fre
         ws = _WORKSPACES[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     coef = torch.empty((B, Xo, Yo, Zo), dtype=torch.float32, device=dev)
     out = torch.empty((2,), dtype=torch.float32, device=dev)
-    _lib.launch('veon_occ_bin_loss_fwd', dev, bin_low, _strides(bin_low), B, zi, yi, xi, Zo,
+    _lib.launch('veon_occ_bin_loss_fwd', dev, bin_low, _lib.strides(bin_low), B, zi, yi, xi, Zo,
                 Yo, Xo, labels, class_weights, int(ignore_index), int(free_index), coef, ws,
                 nbytes, out)
     return coef, out

@@ -63,11 +63,8 @@ def occ_labels(sem_low, bin_low, occ_size, gt=None, mask=None, hist=None):
         assert hist.dtype == torch.int64 and hist.is_contiguous()
         assert hist.numel() == (Q + 1) * (Q + 1), (tuple(hist.shape), Q)
     labels = torch.empty((B, Xo, Yo, Zo), dtype=torch.uint8, device=dev)
-    s5 = ctypes.c_int64 * 5
-    ss, bs = s5(*sem_low.stride()), s5(*bin_low.stride())
-    _lib.launch('veon_occ_labels', dev, sem_low, ctypes.cast(ss, ctypes.c_void_p), Q,
-                bin_low, ctypes.cast(bs, ctypes.c_void_p), B, zi, yi, xi, Zo, Yo, Xo,
-                labels, gt, mask, hist)
+    _lib.launch('veon_occ_labels', dev, sem_low, _lib.strides(sem_low), Q, bin_low,
+                _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, labels, gt, mask, hist)
     return labels
 
 

@@ -14,8 +14,6 @@ every point interpolates from the 8 low-resolution rows it needs, so the upsampl
 volume (1.31 GB at C = 512) is never formed.  On CPU it runs the reference sequence
 in torch (the fallback, and the CPU tests' oracle).  Prompt embeddings are inputs
 (the text encoder is not part of this package)."""
-import ctypes
-
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -106,12 +104,9 @@ def retrieve_points(feat, bin_low, points, embeddings, occ_size, batch=0):
     prob = (torch.empty((P,), dtype=torch.float32, device=dev)
             if bin_low is not None else None)
     norms = torch.empty((Q,), dtype=torch.float32, device=dev)
-    s5 = ctypes.c_int64 * 5
-    fs = s5(*view.stride())
-    bs = s5(*(bin_low.stride() if bin_low is not None else (0,) * 5))
-    _lib.launch('veon_occ_retrieve', dev, view, is_half, ctypes.cast(fs, ctypes.c_void_p), C,
-                bin_low, ctypes.cast(bs, ctypes.c_void_p), B, zi, yi, xi, Zo, Yo, Xo, pts, P,
-                batch, emb, Q, norms, score, prob)
+    bs = _lib.strides(bin_low) if bin_low is not None else _lib.host_array((0,) * 5)
+    _lib.launch('veon_occ_retrieve', dev, view, is_half, _lib.strides(view), C, bin_low, bs,
+                B, zi, yi, xi, Zo, Yo, Xo, pts, P, batch, emb, Q, norms, score, prob)
     return score, prob
 
 
