@@ -19,9 +19,9 @@
  * The ctypes binding (veon_amd/_lib.py) reads its argument types from THIS file, so
  * every declaration below keeps to one style: C89 prototypes `ret veon_name(args);`
  * (they may span lines) with ret in {int, int64_t, void, const char *} and parameters
- * int / int64_t / float / double / unsigned or a pointer (any pointer is passed as an address);
- * `(void)` for no parameters; comments are C block comments; the only other statement
- * is the one `typedef struct`.  Anything else makes the binding raise at import.
+ * int / int64_t / float / double / unsigned, a pointer (any pointer is passed as an address)
+ * or veon_image_windows by value; `(void)` for no parameters; comments are C block
+ * comments; the only other statements are the two `typedef struct`s.  Anything else makes the binding raise at import.
  * Prototypes are grouped by the source file under veon_amd/csrc/ that defines them;
  * every entry point that launches work ends in `void *stream`.
  */
@@ -1415,6 +1415,68 @@ int veon_lidar_depth_render(const float *points, int B, int P, int row_stride,
                             const float *lidar2img, const float *post_rots,
                             const float *post_trans, int N, int H, int W, int downsample,
                             int block, float lo, float hi, float *out, void *stream);
+
+/* ======== image_inputs.hip ========================================================== */
+
+/* The camera inputs of the pipeline step PrepareImageInputs (datasets/pipelines/
+ * loading.py:1073-1329) from decoded frames: Pillow's 8-bit bicubic Image.resize bit for
+ * bit, the crop window, the optional column mirror, the normalised planes, and the
+ * depthanythingv2 tail of the depth branch.  All tensors contiguous.
+ *
+ * Resampling tables of one axis, in -> out (veon_amd/image_inputs.py resize_coeffs, Pillow's
+ * precompute_coeffs + normalize_coeffs_8bpc): bounds (out,2) int32 = first tap and tap count
+ * of each output index, kk (out,ksize) int32 = the coefficients in 22-bit fixed point.  One
+ * pass is  ss = 2^21 + sum_t pixel[first + t] * kk[t];  out = clamp(ss >> 22, 0, 255)  in
+ * 32-bit integers.  The kernels clamp first / count to the source extent, so a wrong table
+ * cannot make them read outside it.  BN, rows, fH, oh in 1 .. 65535. */
+
+#define VEON_IMAGE_MAX_WINDOWS 32
+
+/* Window origins inside the resized image and column mirrors, by value: image bn of a call
+ * uses entry bn % n (n = 1: one window for all; n = N: one per camera of every sample). */
+typedef struct veon_image_windows {
+  int n;
+  int x0[VEON_IMAGE_MAX_WINDOWS];
+  int y0[VEON_IMAGE_MAX_WINDOWS];
+  int flip[VEON_IMAGE_MAX_WINDOWS];
+} veon_image_windows;
+
+/* Horizontal pass of source rows row0 .. row0 + rows - 1 only (the rows the vertical pass of
+ * the windows reads): frames (BN,H,W,3) uint8 -> tmp (BN,rows,Wo,3) uint8. */
+int veon_image_resample_h(const uint8_t *frames, int BN, int H, int W, int Wo, int row0,
+                          int rows, const int *bounds, const int *kk, int ksize,
+                          uint8_t *tmp, void *stream);
+
+/* Vertical pass on the windows and the finish.  src (BN,Hs,Ws,3) uint8 holds rows
+ * row0 .. row0 + Hs - 1 of the horizontally resized image (tmp above, or the frames
+ * themselves with row0 = 0 when the width does not change); Ho is the resized height and
+ * bounds / kk its tables (Ho rows).  bounds == NULL: no vertical pass (a pass whose size
+ * does not change is skipped, as in Pillow): window row y is source row y0 + y.
+ * Window pixel (y, x) of image bn is resized pixel (y0 + y, x0 + (flip ? fW - 1 - x : x)).
+ * Writes either or both of
+ *   canvas (BN,fH,fW,3) uint8: the transformed image (the reference's `canvas`);
+ *   planes (BN,3,fH,fW) fp32:  planes[c] = lut[c][canvas[..., swap ? 2 - c : c]], lut
+ *                              (3,256) fp32 on the device (the reference's normalisation
+ *                              is a function of a byte; the host tabulates it).
+ * A window outside the resized image (or outside src when bounds == NULL), n outside
+ * 1 .. 32, both outputs NULL: VEON_ERR_BAD_ARG.  Every element of the outputs given is
+ * written; one launch, no workspace, capturable. */
+int veon_image_resample_v_finish(const uint8_t *src, int BN, int Hs, int Ws, int row0,
+                                 int Ho, const int *bounds, const int *kk, int ksize,
+                                 veon_image_windows win, int fH, int fW, const float *lut,
+                                 int swap, uint8_t *canvas, float *planes, void *stream);
+
+/* depthanythingNormalize's tail (loading.py:1048-1069): src (BN,h,w,3) uint8 -> out
+ * (BN,3,oh,ow) fp32.  Channel c reads src channel swap ? 2 - c : c; x = u / 255; cubic
+ * resize by OpenCV's INTER_CUBIC rule as far as it is stated here:
+ *   fx = (float)((dx + 0.5) * ((double)w / ow) - 0.5), sx = floor(fx), t = fx - sx, A = -0.75
+ *   w0 = ((A (t+1) - 5A)(t+1) + 8A)(t+1) - 4A,  w1 = ((A+2) t - (A+3)) t t + 1,
+ *   w2 = w1 at 1 - t,  w3 = 1 - w0 - w1 - w2;  taps sx - 1 .. sx + 2 clamped to the image;
+ *   rows first (taps summed left to right), then columns;
+ * then (x - mean[c]) / std[c].  fp32, one rounding per operation. */
+int veon_image_cubic_norm(const uint8_t *src, int BN, int h, int w, int oh, int ow, int swap,
+                          float mean0, float mean1, float mean2, float std0, float std1,
+                          float std2, float *out, void *stream);
 
 /* ======== occ_bin_loss.hip ========================================================== */
 

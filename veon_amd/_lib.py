@@ -40,6 +40,16 @@ class VitBlockWeights(ctypes.Structure):
                 ('q_log2', ctypes.c_int)]
 
 
+IMAGE_MAX_WINDOWS = 32
+
+
+class ImageWindows(ctypes.Structure):
+    """``veon_image_windows`` of include/veon_hip.h, passed by value."""
+    _fields_ = [('n', ctypes.c_int), ('x0', ctypes.c_int * IMAGE_MAX_WINDOWS),
+                ('y0', ctypes.c_int * IMAGE_MAX_WINDOWS),
+                ('flip', ctypes.c_int * IMAGE_MAX_WINDOWS)]
+
+
 LAYOUT_BZYXC = 0
 LAYOUT_BCZYX = 1
 FEAT_F32, FEAT_F16, FEAT_BF16 = 0, 1, 2
@@ -50,7 +60,8 @@ class VeonHipError(RuntimeError):
 
 
 _C_TYPES = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
-            'double': ctypes.c_double, 'unsigned': ctypes.c_uint}
+            'double': ctypes.c_double, 'unsigned': ctypes.c_uint,
+            'veon_image_windows': ImageWindows}
 
 
 def _ctype(decl, is_return=False):
