@@ -21,7 +21,7 @@
  * (they may span lines) with ret in {int, int64_t, void, const char *} and parameters
  * int / int64_t / float / double / unsigned, a pointer (any pointer is passed as an address)
  * or veon_image_windows by value; `(void)` for no parameters; comments are C block
- * comments; the only other statements are the two `typedef struct`s.  Anything else makes the binding raise at import.
+ * comments; the only other statements are the three `typedef struct`s.  Anything else makes the binding raise at import.
  * Prototypes are grouped by the source file under veon_amd/csrc/ that defines them;
  * every entry point that launches work ends in `void *stream`.
  */
@@ -1613,6 +1613,61 @@ int veon_volume_sigm_bwd_pack_cl(const float *grad, const int64_t *grad_strides,
                                  const void *f_storage, void *out_storage,
                                  int64_t guard_rows, int B, int C, int Z, int Y, int X,
                                  void *stream);
+
+/* ======== optim_step.hip ============================================================ */
+
+/* The parameter update of a training iteration: clip_grad_norm_(max_norm, norm_type = 2),
+ * AdamW (the configs under configs/veon: lr 1e-4, weight_decay 1e-2, grad_clip max_norm 5) and the
+ * weight EMA of MEGVIIEMAHook (mmdet3d/core/hook/ema.py:48-59) over flat fp32 arenas.
+ * fp32 only; no atomics, no read-back, no allocation, every call bit-reproducible.
+ *
+ * The gradients, exp_avg and exp_avg_sq of every trained tensor live at the same element
+ * offset of three arenas of n floats, n a multiple of veon_optim_chunk() (4096), each
+ * tensor's slot starting at a multiple of 4 elements, padding zero, bases 16-byte aligned.
+ *
+ * veon_optim_sumsq: partials[c] = sum of squares of chunk c of grad (n / chunk partials),
+ * in the fixed order csrc/optim_step.hip states.
+ * veon_optim_clip_finish (one workgroup): adds the partials in fp64 in a fixed order,
+ *   scal[0] = norm = fp32(sqrt(sum)),  scal[1] = coef = min(max_norm / (norm + 1e-6f), 1)
+ * where a NaN stays NaN (clip_grad_norm_ with error_if_nonfinite=False); max_norm > 0.
+ *
+ * veon_optim_update: one workgroup per record (the grid is capped and strides).  A record
+ * is at most one chunk of one tensor: p and ema point at the piece's first element, offset
+ * is its element offset in the arenas, count its length (1 .. chunk), group its row of the
+ * per-group scalars.  ema == NULL: no EMA of this piece.  offset == -1: EMA-only (a buffer
+ * or a frozen parameter; p is only read).  16-byte accesses where p and ema are 16-byte
+ * aligned, element accesses otherwise.  The table is on the device.  scal: the buffer of
+ * veon_optim_clip_finish, or NULL for coef = 1.  host_scalars: HOST doubles, rounded to fp32
+ * here: {c_d, c_1md} and then VEON_OPTIM_GROUP_SCALARS per group, {c_decay, c_1mb1, c_b2,
+ * c_1mb2, c_step, c_bc2, c_eps}; n_groups <= VEON_OPTIM_MAX_GROUPS (0: grad, exp_avg and
+ * exp_avg_sq may be NULL and every record must be EMA-only).  Per element, in this order:
+ *   g = grad * coef
+ *   p = p * c_decay                                 c_decay = 1 - lr * weight_decay
+ *   m = m + c_1mb1 * (g - m)                        c_1mb1  = 1 - beta1
+ *   v = v * c_b2 + c_1mb2 * (g * g)                 c_b2 = beta2, c_1mb2 = 1 - beta2
+ *   p = p - c_step * (m / (sqrtf(v) / c_bc2 + c_eps))
+ *                                  c_step = lr / (1 - beta1^t), c_bc2 = sqrt(1 - beta2^t)
+ *   e = e * c_d + c_1md * p                         c_d = d, c_1md = 1.0 - d
+ * The clipped gradient is not stored: nothing reads it before the next zero_grad.  The
+ * per-step scalars are launch arguments, so a captured graph would replay one step's
+ * values: the step is launched, not replayed. */
+#define VEON_OPTIM_MAX_GROUPS 8
+#define VEON_OPTIM_GROUP_SCALARS 7
+typedef struct veon_optim_record {
+  float *p;
+  float *ema;
+  int64_t offset;
+  int32_t count;
+  int32_t group;
+} veon_optim_record;
+int veon_optim_chunk(void);
+int veon_optim_sumsq(const float *grad, int64_t n, float *partials, void *stream);
+int veon_optim_clip_finish(const float *partials, int64_t n_partials, double max_norm,
+                           float *scal, void *stream);
+int veon_optim_update(const veon_optim_record *records, int64_t n_records,
+                      const float *grad, float *exp_avg, float *exp_avg_sq,
+                      const float *scal, const double *host_scalars, int n_groups,
+                      void *stream);
 
 /* ======== memory.hip ================================================================ */
 
