@@ -1179,6 +1179,44 @@ int veon_occ_confusion(const void *pred, int pred_elem_bytes, const uint8_t *gt,
                        const uint8_t *mask, int64_t n, int n_cl, int64_t *hist, int *flag,
                        void *stream);
 
+/* ======== occ_classify_grouped.hip ================================================== */
+
+/* The two tails against a detailed vocabulary (SANInVeonTemporal._merge_classes_prob,
+ * san_in_veon_entry_temporal.py:273-297, then veon_temporal.py:220-229): sem holds K
+ * low-resolution logit rows (strides, extents and interpolation as veon_occ_classify),
+ * group (a HOST array of K bytes) names the merged channel of each row.
+ *   - The rows of one merged channel are CONSECUTIVE, and every channel in [0, n_merged)
+ *     has exactly one run; which run feeds which channel is otherwise free (the
+ *     background run may come first or last).  Anything else: VEON_ERR_BAD_ARG.
+ *   - merged value = the maximum over the run's UPSAMPLED rows, NaN if one of them is NaN
+ *     (torch.max);
+ *   - label = the lowest merged channel that attains the maximum merged value;
+ *   - scored = no NaN in any of the K rows and a finite maximum;
+ *     keep = scored and softmax(upsampled bin)[0] > 0.5; a voxel that is not kept gets
+ *     free_label (0 <= free_label <= 255, need not be n_merged - 1).
+ *   - 1 <= K <= 256, 1 <= n_merged <= 64, B*Zo*Yo*Xo < 2^31.
+ * The K upsampled rows are never written.  No memset, no allocation, no read-back; every
+ * output element is written; the only atomics are the histogram's integer ones.
+ *
+ * veon_occ_labels_grouped: labels (B,Xo,Yo,Zo) uint8 only, Zo <= 2048; gt / mask / hist as
+ * veon_occ_labels with n_cl = max(n_merged, free_label + 1) <= 64: hist (n_cl*n_cl int64)
+ * is accumulated into. */
+int veon_occ_labels_grouped(const float *sem, const int64_t *sem_strides, int K,
+                            const uint8_t *group, int n_merged, int free_label,
+                            const float *bin, const int64_t *bin_strides, int B, int zi,
+                            int yi, int xi, int Zo, int Yo, int Xo, uint8_t *labels,
+                            const uint8_t *gt, const uint8_t *mask, int64_t *hist,
+                            void *stream);
+
+/* veon_occ_classify_grouped: the same labels as cls_out (B,Xo,Yo,Zo) int64, the upsampled
+ * occupancy pair bin_out (B,2,Zo,Yo,Xo) and the MERGED logits merged_out
+ * (B,n_merged,Zo,Yo,Xo) fp32, each channel stored once, when its run ends. */
+int veon_occ_classify_grouped(const float *sem, const int64_t *sem_strides, int K,
+                              const uint8_t *group, int n_merged, int free_label,
+                              const float *bin, const int64_t *bin_strides, int B, int zi,
+                              int yi, int xi, int Zo, int Yo, int Xo, float *merged_out,
+                              float *bin_out, int64_t *cls_out, void *stream);
+
 /* ======== occ_fscore.hip ============================================================ */
 
 /* The counts of Metric_FScore (mmdet3d/datasets/occ_metrics.py:150-237) without its

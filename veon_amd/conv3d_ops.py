@@ -940,3 +940,28 @@ def occ_classify(sem_low, bin_low, occ_size):
     _lib.launch('veon_occ_classify', dev, sem_low, _lib.strides(sem_low), Q, bin_low,
                 _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, sem, binv, cls)
     return sem, binv, cls
+
+
+def occ_classify_grouped(sem_low, bin_low, occ_size, group, n_merged, free_label):
+    """``occ_classify`` against a detailed vocabulary (``occ_eval.occ_labels_grouped``
+    states the rule): K logit rows ``sem_low`` (B,K,z,y,x), ``group`` the merged channel of
+    each row.  -> (merged logits (B,n_merged,Z,Y,X), bin_occ (B,2,Z,Y,X), occ_pred_cls
+    (B,X,Y,Z) int64); the K upsampled rows are never written.  Native on a ROCm device,
+    ``occ_eval.occ_grouped_reference`` on the CPU."""
+    from . import occ_eval
+    B, K, zi, yi, xi = sem_low.shape
+    group = occ_eval.group_table(group, n_merged, free_label, K)
+    assert tuple(bin_low.shape) == (B, 2, zi, yi, xi)
+    if not sem_low.is_cuda:
+        return occ_eval.occ_grouped_reference(sem_low, bin_low, occ_size, group, n_merged,
+                                              free_label)
+    dev = _lib.require_device(sem_low, bin_low)
+    assert sem_low.dtype == bin_low.dtype == torch.float32
+    Zo, Yo, Xo = (int(v) for v in occ_size)
+    merged = torch.empty((B, int(n_merged), Zo, Yo, Xo), dtype=torch.float32, device=dev)
+    binv = torch.empty((B, 2, Zo, Yo, Xo), dtype=torch.float32, device=dev)
+    cls = torch.empty((B, Xo, Yo, Zo), dtype=torch.int64, device=dev)
+    _lib.launch('veon_occ_classify_grouped', dev, sem_low, _lib.strides(sem_low), K,
+                occ_eval._group_arg(group), int(n_merged), int(free_label), bin_low,
+                _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, merged, binv, cls)
+    return merged, binv, cls

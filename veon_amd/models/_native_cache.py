@@ -35,3 +35,12 @@ class NativeCacheMixin:
     def _apply(self, fn, *args, **kwargs):
         self.invalidate_hip_cache()
         return super()._apply(fn, *args, **kwargs)
+
+
+def invalidate_all(module):
+    """``invalidate_hip_cache`` of ``module`` and of every sub-module that has one: for a
+    change no nn.Module event announces (``VeonOccupancyPath.set_vocabulary``)."""
+    for m in module.modules():
+        drop = getattr(m, 'invalidate_hip_cache', None)
+        if drop is not None:
+            drop()

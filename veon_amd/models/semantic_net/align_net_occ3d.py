@@ -60,6 +60,9 @@ class AlignNetOcc3D(nn.Module):
     # ``_body`` lives in __dict__ (its blocks are registered once, above), so nn.Module
     # does not recurse into it: the three events that drop its folded weights are
     # forwarded by hand
+    def invalidate_hip_cache(self):
+        self.__dict__['_body'].invalidate_hip_cache()
+
     def train(self, mode=True):
         self.__dict__['_body'].train(mode)
         return super().train(mode)

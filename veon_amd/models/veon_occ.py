@@ -15,8 +15,9 @@ package's mirrors (single frame, inference):
 
 NOT included (third-party / not rebuilt): the timm side-adapter ViT, its mask
 decoder and the 2-D segmentation outputs (``sem_embed_ds`` only supplies a shape
-to the decoder), the text encoder (class embeddings are an input).  Weights are
-whatever the sub-modules hold (random unless loaded).
+to the decoder).  Weights are whatever the sub-modules hold (random unless loaded); the
+classifier rows are ``ov_classifier_weight`` (random) until ``set_vocabulary`` hands the
+path a text classifier (``semantic_net.clip_text.OvClassifier``) and a vocabulary.
 
 Temporal (``num_temporal > 1``, san_in_veon_temporal.py:158-173): ``lift_frame``
 gives a past frame's lifted volume (``forward_early``), ``align`` warps it into
@@ -111,6 +112,11 @@ class VeonOccupancyPath(nn.Module):
         self.occ_decoder.two_hot_eps = sparse_lift_eps
         self.occ_decoder.num_frame, self.occ_decoder.num_camera = 1, num_cam
         self.ov_classifier_weight = nn.Parameter(torch.randn(n_classes, clip_proj_dim))
+        # set_vocabulary: the (K2 + 1, C) rows of a detailed vocabulary (moves with the
+        # module, stays out of the state dict) and, in __dict__, what goes with them
+        self.register_buffer('ov_vocab_weight', None, persistent=False)
+        self.__dict__['_ov'] = None
+        self.vocabulary_version = 0
         self.input_size, self.num_cam, self.occ_size = input_size, num_cam, occ_size
         self.two_streams = two_streams
         if bf16_heads:
@@ -119,6 +125,50 @@ class VeonOccupancyPath(nn.Module):
             for layer in self.occ_decoder.fusion_layers.values():
                 layer.hip_dtype = _half.dtype()
         self.__dict__['_side'] = None
+
+    # ----------------------------------------------------------- vocabulary
+    def set_vocabulary(self, classifier, vocabulary, class_reflection):
+        """Classify against a detailed vocabulary, as the reference does
+        (``prepare_vocabulary``, san_in_veon_temporal.py:261-266, and
+        ``_merge_classes_prob`` + ``simple_test``): ``classifier`` (an ``OvClassifier``)
+        turns the K2 descriptions ``vocabulary`` into the (K2 + 1, C) classifier rows, the
+        learnable background row last; consecutive equal values of ``class_reflection``
+        (K2 ints, ``vocabulary.build_vocabulary``) form one merged class.  From then on the
+        tails take the maximum over each run of rows and arg-max the merged channels
+        (``occ_eval.occ_labels_grouped`` / ``conv3d_ops.occ_classify_grouped``): n_runs + 1
+        channels, the background channel last, ``free_label`` = n_runs; ``evaluate`` counts
+        n_runs + 1 classes, ``occ_loss`` receives the same rows and ``class_reflection``,
+        and ``retrieve(..., prompts=[...])`` encodes its prompts through ``classifier``.
+
+        Every native cache of the path is dropped and ``vocabulary_version`` is bumped: a
+        hipGraph captured from the path before the call still holds the old rows and must
+        be captured again (``CameraShardedStep`` refuses to replay).  A path on which this
+        is never called is unchanged in every output and bit."""
+        from ..align_select import group_ids
+        from ..occ_eval import group_table
+        from ._native_cache import invalidate_all
+        vocabulary = list(vocabulary)
+        if len(class_reflection) != len(vocabulary):
+            raise ValueError('%d descriptions but %d entries of class_reflection'
+                             % (len(vocabulary), len(class_reflection)))
+        gid, n_runs = group_ids(class_reflection)
+        group = group_table(gid + [n_runs], n_runs + 1, n_runs)
+        weight = classifier.classifier_weight(vocabulary)
+        C = self.ov_classifier_weight.shape[1]
+        if tuple(weight.shape) != (len(vocabulary) + 1, C):
+            raise ValueError('the classifier gives rows of shape %s, the path needs %s'
+                             % (tuple(weight.shape), (len(vocabulary) + 1, C)))
+        self.ov_vocab_weight = weight.detach().to(self.ov_classifier_weight.device,
+                                                  torch.float32).contiguous()
+        self.__dict__['_ov'] = dict(classifier=classifier, vocabulary=vocabulary,
+                                    class_reflection=[int(v) for v in class_reflection],
+                                    group=group, n_merged=n_runs + 1, free_label=n_runs)
+        invalidate_all(self)
+        self.vocabulary_version += 1
+
+    def _classifier_weight(self):
+        return self.ov_classifier_weight if self.__dict__['_ov'] is None \
+            else self.ov_vocab_weight
 
     # ------------------------------------------------------------- branches
     def estimate_depth(self, img, num_cam=None):
@@ -179,7 +229,7 @@ class VeonOccupancyPath(nn.Module):
         for i, t in enumerate(outs):
             ClipRecHead._save(feats, i, t, hw)
         return semantic_branch_2d(self.side_adapter_network, self.clip_rec_head,
-                                  self.ov_classifier_weight, img, feats)
+                                  self._classifier_weight(), img, feats)
 
     def _branches(self, images, depth=None, metas=None):
         """Both encoder branches of one frame -> (CLIP feature dict, supp, depth).
@@ -279,13 +329,36 @@ class VeonOccupancyPath(nn.Module):
         ``VEONTemporal.simple_test`` returns, veon_temporal.py:219-241) and neither
         ``sem_occ`` nor ``bin_occ``; the upsampled volumes are then not written at all on
         the native path.  ``count`` (with ``labels_only``): (gt, mask or None, hist) of
-        ``occ_eval.occ_labels`` -- the labels' confusion matrix is added to ``hist``."""
+        ``occ_eval.occ_labels`` -- the labels' confusion matrix is added to ``hist``.
+        After ``set_vocabulary``: the grouped tails, ``sem_occ`` holds the MERGED logits."""
         from .. import conv3d_ops, occ_eval
-        W = self.ov_classifier_weight
+        W = self._classifier_weight()
         extra = {'feat_low': feat, 'bin_low': bin_occ} if return_features else {}
         if count is not None and not labels_only:
             raise ValueError('count needs labels_only=True')
         native = bin_occ.is_cuda and not torch.is_grad_enabled() and bin_occ.shape[1] == 2
+        ov = self.__dict__['_ov']
+        if ov is not None:
+            merge = (ov['group'], ov['n_merged'], ov['free_label'])
+            low = classifier_logits_low(W, feat).float()
+            gt, mask, hist = count or (None, None, None)
+            if labels_only and (native or not bin_occ.is_cuda):
+                # (on the CPU the wrapper itself is the torch mirror)
+                occ = occ_eval.occ_labels_grouped(low, bin_occ.float(), self.occ_size,
+                                                  *merge, gt, mask, hist)
+                return {'occ_pred_cls': occ, **extra}
+            if native:
+                sem_occ, bin_up, occ = conv3d_ops.occ_classify_grouped(
+                    low, bin_occ.float(), self.occ_size, *merge)
+            else:
+                sem_occ, bin_up, occ = occ_eval.occ_grouped_reference(
+                    low, bin_occ, self.occ_size, *merge)
+            if labels_only:     # a device forward with grad enabled
+                occ = occ.to(torch.uint8)
+                if count is not None:
+                    occ_eval.confusion(occ, gt, mask, hist.shape[0], hist)
+                return {'occ_pred_cls': occ, **extra}
+            return {'bin_occ': bin_up, 'sem_occ': sem_occ, 'occ_pred_cls': occ, **extra}
         if native and labels_only:
             # the same labels, and nothing but the labels, from one kernel
             low = classifier_logits_low(W, feat)
@@ -299,7 +372,7 @@ class VeonOccupancyPath(nn.Module):
             sem_occ, bin_up, occ = conv3d_ops.occ_classify(low.float(), bin_occ.float(),
                                                            self.occ_size)
             return {'bin_occ': bin_up, 'sem_occ': sem_occ, 'occ_pred_cls': occ, **extra}
-        sem_occ = semantic_inference_3d_fused(self.ov_classifier_weight, feat, self.occ_size)
+        sem_occ = semantic_inference_3d_fused(W, feat, self.occ_size)
         bin_occ = F.interpolate(bin_occ, size=tuple(self.occ_size), mode='trilinear',
                                 align_corners=False)
         # veon_temporal.py:219-227
@@ -447,14 +520,23 @@ class VeonOccupancyPath(nn.Module):
         return self._classify(dec.occupancy_pred(xx), dec.feat_pred(xx), return_features,
                               labels_only)
 
-    def retrieve(self, out, points_indices, embeddings, batch=0):
+    def retrieve(self, out, points_indices, embeddings=None, batch=0, prompts=None):
         """Open-vocabulary point retrieval (the reference's ``retrieval=True`` branch,
         veon_temporal.py:232-241, 331-356) on the output of ``forward(...,
         return_features=True)``: ``points_indices`` (P, 3) int32 (x, y, z) voxels of the
         evaluation grid (``retrieval.points_to_voxel_indices``), ``embeddings`` (Q, C)
         prompt embeddings -> (score (Q, P), bin_prob (P,)); see
-        ``retrieval.retrieve_points``."""
+        ``retrieval.retrieve_points``.  ``prompts`` (a list of strings, after
+        ``set_vocabulary``) instead of ``embeddings``: encoded by the vocabulary's
+        classifier (``OvClassifier.retrieval_embedding``, san_in_veon_temporal.py:268-273)."""
         from ..retrieval import retrieve_points
+        if (embeddings is None) == (prompts is None):
+            raise ValueError('retrieve takes either embeddings or prompts')
+        if prompts is not None:
+            if self.__dict__['_ov'] is None:
+                raise RuntimeError('retrieve(prompts=...) needs set_vocabulary first')
+            embeddings = self.__dict__['_ov']['classifier'].retrieval_embedding(
+                list(prompts)).to(out['bin_low'].device, torch.float32)
         return retrieve_points(out['feat_low'], out['bin_low'], points_indices, embeddings,
                                self.occ_size, batch)
 
@@ -470,16 +552,22 @@ class VeonOccupancyPath(nn.Module):
         (images, sensor2egos, ego2globals, intrins, post_rots, post_trans, bda,
         lidar2lidarego, lidarego2global, cam2camego, camego2global); ``sem_seg_ds``
         (B, N, K2, h, w): the 2-D branch's class logits; ``class_reflection``: merged
-        class of each of its K2 classes.  ``prev_img_inputs`` is accepted and unused, as
+        class of each of its K2 classes (None after ``set_vocabulary``: the vocabulary's,
+        and the loss then gets the vocabulary's K2 + 1 rows).  ``prev_img_inputs`` is
+        accepted and unused, as
         in the reference.  -> dict of ``loss_binocc_c_0``, ``loss_featalign_det_c_0``,
         ``loss_featalign_soft_c_0`` (the reference's rule for leaving a key out)."""
         feat = out['feat_low']
         if not isinstance(feat, torch.Tensor):
             raise TypeError('occ_loss needs the torch heads\' feat_low (a forward with grad '
                             'enabled); the no-grad native path returns a PaddedVolume')
+        if class_reflection is None:
+            if self.__dict__['_ov'] is None:
+                raise ValueError('class_reflection=None needs set_vocabulary first')
+            class_reflection = self.__dict__['_ov']['class_reflection']
         results = dict(feat_occ=feat, bin_occ=out['bin_low'], occ_size=self.occ_size,
                        sem_seg_ds=sem_seg_ds, class_reflection=class_reflection,
-                       ov_classifier_weight=self.ov_classifier_weight)
+                       ov_classifier_weight=self._classifier_weight())
         return loss(voxel_semantics, mask_camera, results, img_inputs,
                     prev_img_inputs=prev_img_inputs)
 
@@ -537,7 +625,8 @@ class VeonOccupancyPath(nn.Module):
         if isinstance(metric, (list, tuple, OccFScoreMetric)):
             return self._evaluate_many(images, img_metas, voxel_semantics, mask_camera,
                                        metric, prev_volumes, depth)
-        n_cl = self.ov_classifier_weight.shape[0] + 1
+        ov = self.__dict__['_ov']
+        n_cl = self.ov_classifier_weight.shape[0] + 1 if ov is None else ov['n_merged']
         if metric.num_classes != n_cl:
             raise ValueError('the metric counts %d classes, the path predicts %d (+ free)'
                              % (metric.num_classes, n_cl - 1))
@@ -615,7 +704,7 @@ class VeonOccupancyPath(nn.Module):
     def _add_2d(self, out, images, feats):
         from .semantic_net.side_adapter import semantic_branch_2d
         two_d = semantic_branch_2d(self.side_adapter_network, self.clip_rec_head,
-                                   self.ov_classifier_weight, images.flatten(0, 1), feats)
+                                   self._classifier_weight(), images.flatten(0, 1), feats)
         out = dict(out)
         for k in ('mask_preds', 'mask_logits', 'sem_seg_ds', 'sem_embed_ds', 'sem_seg'):
             out['2d_' + k] = two_d[k]
@@ -644,6 +733,7 @@ class CameraShardedStep:
         if reduce not in ('allreduce', 'scatter'):
             raise ValueError("reduce must be 'allreduce' or 'scatter', got %r" % (reduce,))
         self.dist, self.group = dist, group
+        self.net, self.vocabulary_version = net, net.vocabulary_version
         self.active = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(group) if self.active else 1
         rank = dist.get_rank(group) if self.active else 0
@@ -691,6 +781,9 @@ class CameraShardedStep:
             3 if self.scatter else 2)
 
     def __call__(self, images):
+        if self.net.vocabulary_version != self.vocabulary_version:
+            raise RuntimeError('set_vocabulary was called after this step was captured: '
+                               'its graphs hold the old classifier rows; build a new step')
         dist = self.dist
         buf = self.pre(images)
         if self.scatter:

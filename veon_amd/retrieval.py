@@ -12,8 +12,9 @@ over all points and over the visible ones (``compute_single_retrieval``).
 On a ROCm device ``retrieve_points`` is one native call (csrc/occ_retrieval.hip):
 every point interpolates from the 8 low-resolution rows it needs, so the upsampled
 volume (1.31 GB at C = 512) is never formed.  On CPU it runs the reference sequence
-in torch (the fallback, and the CPU tests' oracle).  Prompt embeddings are inputs
-(the text encoder is not part of this package)."""
+in torch (the fallback, and the CPU tests' oracle).  Prompt embeddings are inputs; the
+text side (``models/semantic_net/clip_text.py``: ``OvClassifier.retrieval_embedding``)
+makes them from prompts, and ``VeonOccupancyPath.retrieve(..., prompts=[...])`` does both."""
 import numpy as np
 import torch
 import torch.nn.functional as F
