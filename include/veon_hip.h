@@ -1707,6 +1707,41 @@ int veon_optim_update(const veon_optim_record *records, int64_t n_records,
                       const float *scal, const double *host_scalars, int n_groups,
                       void *stream);
 
+/* ======== sem2d.hip ================================================================= */
+
+/* The semantic tail of SAN's 2-D branch (mmdet3d/models/semantic_net/
+ * san_in_veon_temporal.py:176-186, 240-255): cls = softmax(mask_logits)[..., :-1] and the
+ * mask embeddings spread over the sigmoid of the Q mask proposals.  All tensors fp32 and
+ * contiguous: mask_logits (B,Q,K+1), mask_embs (B,Q,C), mask_preds (B,Q,h,w).  probs: a
+ * workspace of B*Q*K floats that receives cls (the only workspace; written by every
+ * call, so calls on one stream may share it).  Q <= 256, K + 1 <= 256, B <= 65535,
+ * h * w < 2^23, otherwise VEON_ERR_BAD_ARG.  Every sum over q runs in index order with one
+ * fmaf per term: no atomics, no memset, every output element written, repeated calls
+ * bit-identical.  +-inf in mask_preds is undefined (NaN propagates as in torch).
+ *
+ * veon_sem2d_ds (san_in_veon_temporal.py:176, 248-255): sem_seg_ds (B,K,h,w) and, with
+ * mask_embs, sem_embed_ds (B,C,h,w); mask_embs and sem_embed_ds are given or NULL
+ * together. */
+int veon_sem2d_ds(const float *mask_logits, const float *mask_embs, const float *mask_preds,
+                  int B, int Q, int K, int C, int h, int w, float *probs, float *sem_seg_ds,
+                  float *sem_embed_ds, void *stream);
+/* veon_sem2d_full (san_in_veon_temporal.py:179-185, 240-246): sem_seg (B,K,H,W) =
+ * sum_q cls * sigmoid(bilinear(mask_preds)) with ATen's align_corners=False arithmetic
+ * (scale = in / out in float, src = max(scale * (dst + 0.5) - 0.5, 0), upper tap clamped
+ * to the last pixel); any positive h, w, H, W with H <= 262140.  The (B,Q,H,W) tensor
+ * is never formed. */
+int veon_sem2d_full(const float *mask_logits, const float *mask_preds, int B, int Q, int K,
+                    int h, int w, int H, int W, float *probs, float *sem_seg, void *stream);
+/* veon_sem2d_labels (san_in_veon_temporal.py:179-185, 240-246, then the arg-max a caller
+ * takes): uint8 labels (B,H,W) of the values veon_sem2d_full writes (the same arithmetic,
+ * bit for bit), and nothing else.  group (HOST, K bytes, or NULL): the merged channel of
+ * every row as in veon_occ_labels_grouped, n_merged <= 64; each run of rows is merged by
+ * its maximum.  The label is the lowest (merged) channel that attains the maximum; a
+ * pixel with a NaN in any row gets ignore_label (0 .. 255). */
+int veon_sem2d_labels(const float *mask_logits, const float *mask_preds, int B, int Q, int K,
+                      int h, int w, int H, int W, const uint8_t *group, int n_merged,
+                      int ignore_label, float *probs, uint8_t *labels, void *stream);
+
 /* ======== memory.hip ================================================================ */
 
 /* Physically contiguous device memory (hipExtMallocWithFlags +

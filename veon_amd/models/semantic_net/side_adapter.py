@@ -405,23 +405,46 @@ def semantic_inference_2d_w_embed(mask_cls, mask_embed, mask_pred):
     return semseg, semembed
 
 
-def semantic_branch_2d(side_net, rec_head, ov_classifier_weight, images, clip_feats):
+def semantic_branch_2d(side_net, rec_head, ov_classifier_weight, images, clip_feats,
+                       native_tail=False, full=True, labels=False, group=None,
+                       n_merged=None):
     """The 2-D open-vocabulary branch of SANInVeonTemporal.forward
     (san_in_veon_temporal.py:123-139, 176-186) on one flattened camera batch
     ``images`` (B*N,3,H,W) and the CLIP feature dict of layers 0..K: mask proposals
     and attention biases from the side adapter, mask embeddings from the CLIP
     recognition head, class logits against the text embeddings, and the
-    down-sampled / full-resolution semantic maps."""
+    down-sampled / full-resolution semantic maps.
+
+    ``native_tail``: the three maps come from ``veon_amd.sem2d`` (one fused pass each on a
+    ROCm device, the same torch lines on the CPU or under autograd) instead of the lines
+    below.  Then ``full=False`` leaves ``sem_seg`` out (a training step reads only
+    ``sem_seg_ds``) and ``labels=True`` adds ``labels_2d``, uint8 (B*N,H,W): the arg-max of
+    ``sem_seg``, over the runs of rows of ``group`` / ``n_merged``
+    (``occ_eval.group_table``) when a detailed vocabulary is set."""
     mask_preds, attn_biases, san_feats = side_net(images, clip_feats)
     mask_embs = [rec_head(clip_feats, ab, normalize=True) for ab in attn_biases]
     mask_logits = [torch.einsum('bqc,nc->bqn', e, ov_classifier_weight) for e in mask_embs]
+    out = {'mask_preds': mask_preds[-1], 'attn_biases': attn_biases[-1],
+           'mask_embs': mask_embs[-1], 'mask_logits': mask_logits[-1],
+           'san_features': san_feats}
+    if native_tail:
+        from ... import sem2d
+        size = tuple(images.shape[-2:])
+        out['sem_seg_ds'], out['sem_embed_ds'] = sem2d.semantic_maps_ds(
+            mask_logits[-1], mask_embs[-1], mask_preds[-1])
+        if full:
+            out['sem_seg'] = sem2d.semantic_map(mask_logits[-1], mask_preds[-1], size)
+        if labels:
+            out['labels_2d'] = sem2d.semantic_labels(mask_logits[-1], mask_preds[-1], size,
+                                                     group, n_merged)
+        return out
+    if not full or labels:
+        raise ValueError('full=False and labels=True need native_tail=True')
     sem_seg_ds, sem_embed_ds = semantic_inference_2d_w_embed(mask_logits[-1], mask_embs[-1],
                                                              mask_preds[-1])
     up = F.interpolate(mask_preds[-1], size=images.shape[-2:], mode='bilinear',
                        align_corners=False)
     sem_seg = torch.einsum('bqc,bqhw->bchw', F.softmax(mask_logits[-1], dim=-1)[..., :-1],
                            up.sigmoid())
-    return {'mask_preds': mask_preds[-1], 'attn_biases': attn_biases[-1],
-            'mask_embs': mask_embs[-1], 'mask_logits': mask_logits[-1],
-            'sem_seg_ds': sem_seg_ds, 'sem_embed_ds': sem_embed_ds, 'sem_seg': sem_seg,
-            'san_features': san_feats}
+    out.update({'sem_seg_ds': sem_seg_ds, 'sem_embed_ds': sem_embed_ds, 'sem_seg': sem_seg})
+    return out

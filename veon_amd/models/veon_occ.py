@@ -50,6 +50,10 @@ class VeonOccupancyPath(nn.Module):
                   clip_first_tail=18, clip_proj_dim=768, clip_patch=14, clip_image=336,
                   hsa_fusion_map=('0->3->6', '1->9->12', '2->15->18'))
 
+    # the semantic maps of the 2-D branch (``forward_2d``, ``forward(with_2d=True)``) from
+    # the fused kernels of veon_amd/sem2d.py instead of the reference's torch lines
+    hip_tail_2d = False
+
     def __init__(self, input_size=(256, 704), grid_config=None, num_cam=6,
                  encoder='vitb', n_classes=17, clip_width=768, clip_layers=12,
                  clip_heads=12, clip_first_tail=9, clip_proj_dim=512, embed_dim=256,
@@ -214,22 +218,38 @@ class VeonOccupancyPath(nn.Module):
             taps |= set(self.side_adapter_network.fusion_map.values())
         return {t for t in taps if 0 <= t <= self.clip_first_tail}
 
-    def forward_2d(self, images):
+    def _semantic_2d(self, img, feats, full=True, labels=False):
+        """``semantic_branch_2d`` on the flattened images with the path's classifier rows;
+        with ``hip_tail_2d`` the fused tail, which alone knows ``full`` and ``labels``
+        (``labels_2d`` is then taken over the vocabulary's merged classes, if one is set)."""
+        from .semantic_net.side_adapter import semantic_branch_2d
+        args = (self.side_adapter_network, self.clip_rec_head, self._classifier_weight(),
+                img, feats)
+        if not self.hip_tail_2d:
+            if not full or labels:
+                raise ValueError('full=False and labels=True need hip_tail_2d = True')
+            return semantic_branch_2d(*args)
+        ov = self.__dict__['_ov']
+        group = None if ov is None else ov['group'][:-1]   # without the background row
+        return semantic_branch_2d(*args, native_tail=True, full=full, labels=labels,
+                                  group=group, n_merged=None if ov is None else ov['free_label'])
+
+    def forward_2d(self, images, full=True, labels=False):
         """The 2-D open-vocabulary segmentation branch (san_in_veon_temporal.py:
         123-139, 176-186): images (B, N, 3, H, W) -> dict with ``mask_preds``,
         ``mask_embs``, ``mask_logits``, ``sem_seg_ds``, ``sem_embed_ds``, ``sem_seg``.
-        Needs ``side_adapter=True`` at construction."""
+        Needs ``side_adapter=True`` at construction.  With ``hip_tail_2d`` set:
+        ``full=False`` leaves ``sem_seg`` out, ``labels=True`` adds ``labels_2d``, uint8
+        (B*N, H, W)."""
         if self.side_adapter_network is None:
             raise RuntimeError('VeonOccupancyPath was built without side_adapter=True')
-        from .semantic_net.side_adapter import semantic_branch_2d
         img = images.flatten(0, 1)
         x = F.interpolate(img, scale_factor=0.5, mode='bilinear', align_corners=False)
         outs, hw = self.clip_trunk(x, last_layer_idx=self.clip_first_tail)
         feats = {}
         for i, t in enumerate(outs):
             ClipRecHead._save(feats, i, t, hw)
-        return semantic_branch_2d(self.side_adapter_network, self.clip_rec_head,
-                                  self._classifier_weight(), img, feats)
+        return self._semantic_2d(img, feats, full, labels)
 
     def _branches(self, images, depth=None, metas=None):
         """Both encoder branches of one frame -> (CLIP feature dict, supp, depth).
@@ -702,12 +722,12 @@ class VeonOccupancyPath(nn.Module):
         return self._add_2d(out, images, feats) if with_2d else out
 
     def _add_2d(self, out, images, feats):
-        from .semantic_net.side_adapter import semantic_branch_2d
-        two_d = semantic_branch_2d(self.side_adapter_network, self.clip_rec_head,
-                                   self._classifier_weight(), images.flatten(0, 1), feats)
+        two_d = self._semantic_2d(images.flatten(0, 1), feats, labels=self.hip_tail_2d)
         out = dict(out)
         for k in ('mask_preds', 'mask_logits', 'sem_seg_ds', 'sem_embed_ds', 'sem_seg'):
             out['2d_' + k] = two_d[k]
+        if self.hip_tail_2d:
+            out['2d_labels'] = two_d['labels_2d']
         return out
 
 
