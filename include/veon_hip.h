@@ -1132,7 +1132,7 @@ int veon_deform_attention_bwd_dkv_bf16(const void *q_padded, const void *off_pad
                                        int heads, int samples, int off_channels,
                                        void *stream);
 
-/* ======== occ_head.hip ============================================================== */
+/* ======== occ_tail.hip ============================================================== */
 
 /* Tail of the occupancy path in one kernel (semantic_net/san_in_veon_temporal.py:
  * 196-211 + detectors/veon_temporal.py:219-227): sem (B,Q,zi,yi,xi) and bin
@@ -1147,7 +1147,7 @@ int veon_occ_classify(const float *sem, const int64_t *sem_strides, int Q,
                       int yi, int xi, int Zo, int Yo, int Xo, float *sem_out,
                       float *bin_out, int64_t *cls_out, void *stream);
 
-/* ======== occ_eval.hip ============================================================== */
+/* ======== occ_tail.hip (veon_occ_labels), occ_eval.hip (veon_occ_confusion) ========= */
 
 /* The label-only tail: what VEONTemporal.simple_test returns (detectors/
  * veon_temporal.py:219-241 keeps only occ_pred_cls, as uint8).  Inputs, strides, extent
@@ -1179,7 +1179,7 @@ int veon_occ_confusion(const void *pred, int pred_elem_bytes, const uint8_t *gt,
                        const uint8_t *mask, int64_t n, int n_cl, int64_t *hist, int *flag,
                        void *stream);
 
-/* ======== occ_classify_grouped.hip ================================================== */
+/* ======== occ_tail.hip: the grouped tails =========================================== */
 
 /* The two tails against a detailed vocabulary (SANInVeonTemporal._merge_classes_prob,
  * san_in_veon_entry_temporal.py:273-297, then veon_temporal.py:220-229): sem holds K

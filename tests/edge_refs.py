@@ -1,4 +1,4 @@
-"""fp64 CPU references of the sampling kernels (csrc/temporal.hip, csrc/occ_head.hip)
+"""fp64 CPU references of the sampling kernels (csrc/temporal.hip, csrc/occ_tail.hip)
 and the inputs of their edge tests.  A plain module: nothing device-specific, no
 fixtures.  tests/test_edge_refs.py pins every function here on the CPU before the GPU
 modules (tests/test_temporal_edges_gpu.py, tests/test_occ_head_edges_gpu.py) rely on

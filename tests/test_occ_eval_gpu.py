@@ -1,4 +1,4 @@
-"""The label-only tail and the confusion-matrix kernels (csrc/occ_eval.hip).
+"""The label-only tail and the confusion-matrix kernels (csrc/occ_tail.hip, csrc/occ_eval.hip).
 
 Labels: bit-equal to the labels of ``conv3d_ops.occ_classify`` (same code, library built
 without FMA contraction) on every case of tests/edge_refs.py, in both instantiations and

@@ -1,4 +1,4 @@
-"""The grouped tails (csrc/occ_classify_grouped.hip) on the MI355X.
+"""The grouped tails (csrc/occ_tail.hip) on the MI355X.
 
 Yardstick: the EXISTING ``conv3d_ops.occ_classify`` on all K rows, then torch's maximum
 over each run of rows and the lowest channel that attains the maximum.  The kernels blend
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from veon_amd import _lib, conv3d_ops
-from veon_amd.occ_eval import confusion, occ_labels_grouped
+from veon_amd.occ_eval import confusion, occ_labels, occ_labels_grouped
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -134,6 +134,54 @@ def test_labels_and_merged_logits_equal_the_ungrouped_tail(grid, K, layout, bg_f
     assert bool((cls[bad] == free).all())
     kept = (want != free) if K > 1 and not bg_first else ~bad
     assert bool(kept.any())
+
+
+@functools.lru_cache(maxsize=None)
+def _identity_case(K, Zo):
+    """Seeded logits on the (2, 3, 5) grid and what the UNGROUPED tails make of them at
+    (Zo, 7, 10) (non-integer ratios in y and x), computed once and never written: one row
+    NaN in a few voxels, one voxel all -inf; gt with 255s, a mask and their histogram."""
+    size = (Zo, 7, 10)
+    g = torch.Generator().manual_seed(1000 * K + Zo)
+    sem = torch.randn(B, K, 2, 3, 5, generator=g) * 3
+    binv = torch.randn(B, 2, 2, 3, 5, generator=g)
+    for b, z, y, x in ((0, 0, 1, 2), (1, 1, 0, 0), (1, 0, 2, 4)):
+        sem[b, 2, z, y, x] = float('nan')
+    sem[0, :, 1, 2, 3] = float('-inf')
+    shape = (B, size[2], size[1], size[0])
+    gt = torch.randint(0, K + 1, shape, generator=g, dtype=torch.uint8)
+    gt[torch.rand(shape, generator=g) < 0.1] = 255
+    mask = (torch.rand(shape, generator=g) >= 0.3).to(torch.uint8).to(DEV)
+    sem, binv, gt = sem.to(DEV), binv.to(DEV), gt.to(DEV)
+    rows, bin_up, cls = conv3d_ops.occ_classify(sem, binv, size)
+    hist = torch.zeros((K + 1, K + 1), dtype=torch.int64, device=DEV)
+    labels = occ_labels(sem, binv, size, gt, mask, hist)
+    assert torch.equal(labels.long(), cls) and int(hist.sum()) > 0
+    assert bool(torch.isnan(rows).any()) and bool(torch.isneginf(rows).all(1).any())
+    assert bool((cls == K).any()) and bool((cls < K).any())
+    return sem, binv, size, gt, mask, rows, bin_up, cls, labels, hist
+
+
+@pytest.mark.parametrize('Zo', [16, 8, 4, 5])
+@pytest.mark.parametrize('layout', sorted(LAYOUTS))
+@pytest.mark.parametrize('K', [5, 8])
+def test_the_identity_table_gives_the_ungrouped_tails(K, layout, Zo):
+    """group = range(K): every row is a run of its own, so both grouped kernels must give
+    what ``occ_classify`` / ``occ_labels`` give, bit for bit (the merged logits are compared
+    as bit patterns: NaN rows included) -- the four kernels share one voxel body.  K = 5
+    and 8: a 16-byte step with and without surplus floats; Zo = 16, 8, 4, 5: the four widths
+    of the tile writer."""
+    sem, binv, size, gt, mask, rows, bin_up, cls, labels, hist = _identity_case(K, Zo)
+    view = LAYOUTS[layout](sem)
+    table = (list(range(K)), K, K)
+    merged, got_bin, got_cls = conv3d_ops.occ_classify_grouped(view, binv, size, *table)
+    assert torch.equal(got_cls, cls) and torch.equal(got_bin, bin_up)
+    assert torch.equal(merged.view(torch.int32), rows.view(torch.int32))
+    assert torch.equal(occ_labels_grouped(view, binv, size, *table), labels)
+    got_hist = torch.zeros_like(hist)
+    assert torch.equal(occ_labels_grouped(view, binv, size, *table, gt, mask, got_hist),
+                       labels)
+    assert torch.equal(got_hist, hist)
 
 
 @pytest.mark.parametrize('group', [[0, 1], [1, 0], [2, 0, 0, 1]])

@@ -1,4 +1,4 @@
-"""The fused tail of the occupancy path (csrc/occ_head.hip) at its edges, against the
+"""The fused tail of the occupancy path (csrc/occ_tail.hip) at its edges, against the
 float64 reference ``tests/edge_refs.occ_tail_ref`` (pinned on the CPU by
 tests/test_edge_refs.py).  The kernel is fp32 and independent of the half flavour.
 

@@ -1,4 +1,4 @@
-"""The fused tail of the occupancy path (csrc/occ_head.hip) against the reference's
+"""The fused tail of the occupancy path (csrc/occ_tail.hip) against the reference's
 op sequence: F.interpolate(trilinear, align_corners=False) of both logit volumes
 (san_in_veon_temporal.py:196-211), softmax / max / threshold / where / permute of
 VEONTemporal.simple_test (detectors/veon_temporal.py:219-227)."""

@@ -3,9 +3,10 @@
 import json
 import os
 
+import torch
+
 from tests.conftest import GOLD
-from veon_amd.align_select import group_ids
-from veon_amd.vocabulary import build_vocabulary
+from veon_amd.vocabulary import build_vocabulary, group_ids, lowest_argmax, merge_runs
 
 
 def _doc():
@@ -40,3 +41,33 @@ def test_user_words_are_deduplicated_in_order():
         [' B ', 'a', 'b', '', 'A', 'c'], [{'category': 'x', 'detailed_items': [['a'], ['d', 'long d']]}])
     assert voc == ['b', 'a', 'c', 'd'] and reflection == [0, 1, 2, 3]
     assert detailed == ['b', 'a', 'c', "d, in detail 'long d'"]
+
+
+def test_merge_runs_and_lowest_argmax_on_a_hand_written_table():
+    """Three runs over five rows at four positions: a plain one, a tie of channels 1 and 2
+    (the lower wins), a NaN in run 0 (it sticks; no channel attains a NaN maximum: n) and
+    -inf rows."""
+    nan, inf = float('nan'), float('inf')
+    group = [0, 0, 1, 2, 2]
+    rows = torch.tensor([[[1., 0., nan, -inf],
+                          [3., 1., 7., -inf],
+                          [2., 4., 1., -1.],
+                          [0., 4., 2., -2.],
+                          [-1., 2., 3., -inf]]])
+    merged = merge_runs(rows, group, 3)
+    want = torch.tensor([[[3., 1., nan, -inf],
+                          [2., 4., 1., -1.],
+                          [0., 4., 3., -2.]]])
+    torch.testing.assert_close(merged, want, rtol=0, atol=0, equal_nan=True)
+    cls, top = lowest_argmax(merged)
+    assert cls.tolist() == [[0, 1, 3, 1]] and cls.dtype == torch.int64
+    torch.testing.assert_close(top, torch.tensor([[[3., 4., nan, -1.]]]), rtol=0, atol=0,
+                               equal_nan=True)
+    # trailing dims of any number: the same table as a (1, 5, 2, 2) volume
+    cls4, _ = lowest_argmax(merge_runs(rows.view(1, 5, 2, 2), group, 3))
+    assert cls4.tolist() == [[[0, 1], [3, 1]]]
+
+
+def test_group_ids_numbers_runs_in_order_of_appearance():
+    assert group_ids([3, 3, 7, 3]) == ([0, 0, 1, 2], 3)
+    assert group_ids([]) == ([], 0)

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from .retrieval import retrieve_points
+from .vocabulary import group_ids
 
 N_CLS = 17                     # merged classes without the free class (class_num - 1)
 _GRID_KEYS = ('x', 'y', 'z', 'depth')
@@ -29,18 +30,6 @@ _WORKSPACES = {}
 # (device, kind, values) -> small constant tensors (group ids, priorities): uploaded once,
 # so a call copies nothing from the host
 _CONSTANTS = {}
-
-
-def group_ids(class_reflection):
-    """Merged class of every 2-D class: consecutive equal values of ``class_reflection``
-    form one merged class, numbered in order of appearance -> (list, count)."""
-    ref = [int(v) for v in class_reflection]
-    gid, cur = [], -1
-    for i, v in enumerate(ref):
-        if i == 0 or v != ref[i - 1]:
-            cur += 1
-        gid.append(cur)
-    return gid, cur + 1
 
 
 def _check_args(sem_seg, img_inputs, labels, class_reflection, priority, grid_config, occ_size,

@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from . import half as _half
+from .vocabulary import group_table
 
 
 class _PaddedGrid:
@@ -924,22 +925,30 @@ def image_dot(img, w, bias, act='none'):
     return out
 
 
+def _launch_classify(entry, sem_low, bin_low, occ_size, n_out, table):
+    """(n_out channels (B,n_out,Z,Y,X), bin_occ (B,2,Z,Y,X), labels (B,X,Y,Z) int64) from
+    ``entry``; ``table``: the arguments between the row count and ``bin_low`` (none, or
+    the group table's three)."""
+    dev = _lib.require_device(sem_low, bin_low)
+    assert sem_low.dtype == bin_low.dtype == torch.float32
+    B, K, zi, yi, xi = sem_low.shape
+    Zo, Yo, Xo = (int(v) for v in occ_size)
+    sem = torch.empty((B, n_out, Zo, Yo, Xo), dtype=torch.float32, device=dev)
+    binv = torch.empty((B, 2, Zo, Yo, Xo), dtype=torch.float32, device=dev)
+    cls = torch.empty((B, Xo, Yo, Zo), dtype=torch.int64, device=dev)
+    _lib.launch(entry, dev, sem_low, _lib.strides(sem_low), K, *table, bin_low,
+                _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, sem, binv, cls)
+    return sem, binv, cls
+
+
 def occ_classify(sem_low, bin_low, occ_size):
     """Trilinear upsampling (align_corners=False) of the class logits ``sem_low``
     (B,Q,z,y,x) and occupancy logits ``bin_low`` (B,2,z,y,x) -- fp32, ANY strides --
     to ``occ_size``, plus the label volume of VEONTemporal.simple_test, in one kernel.
     -> (sem_occ (B,Q,Z,Y,X), bin_occ (B,2,Z,Y,X), occ_pred_cls (B,X,Y,Z) int64)."""
-    dev = _lib.require_device(sem_low, bin_low)
-    assert sem_low.dtype == bin_low.dtype == torch.float32
     B, Q, zi, yi, xi = sem_low.shape
     assert tuple(bin_low.shape) == (B, 2, zi, yi, xi)
-    Zo, Yo, Xo = (int(v) for v in occ_size)
-    sem = torch.empty((B, Q, Zo, Yo, Xo), dtype=torch.float32, device=dev)
-    binv = torch.empty((B, 2, Zo, Yo, Xo), dtype=torch.float32, device=dev)
-    cls = torch.empty((B, Xo, Yo, Zo), dtype=torch.int64, device=dev)
-    _lib.launch('veon_occ_classify', dev, sem_low, _lib.strides(sem_low), Q, bin_low,
-                _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, sem, binv, cls)
-    return sem, binv, cls
+    return _launch_classify('veon_occ_classify', sem_low, bin_low, occ_size, Q, ())
 
 
 def occ_classify_grouped(sem_low, bin_low, occ_size, group, n_merged, free_label):
@@ -950,18 +959,11 @@ def occ_classify_grouped(sem_low, bin_low, occ_size, group, n_merged, free_label
     ``occ_eval.occ_grouped_reference`` on the CPU."""
     from . import occ_eval
     B, K, zi, yi, xi = sem_low.shape
-    group = occ_eval.group_table(group, n_merged, free_label, K)
+    group = group_table(group, n_merged, free_label, K)
     assert tuple(bin_low.shape) == (B, 2, zi, yi, xi)
     if not sem_low.is_cuda:
         return occ_eval.occ_grouped_reference(sem_low, bin_low, occ_size, group, n_merged,
                                               free_label)
-    dev = _lib.require_device(sem_low, bin_low)
-    assert sem_low.dtype == bin_low.dtype == torch.float32
-    Zo, Yo, Xo = (int(v) for v in occ_size)
-    merged = torch.empty((B, int(n_merged), Zo, Yo, Xo), dtype=torch.float32, device=dev)
-    binv = torch.empty((B, 2, Zo, Yo, Xo), dtype=torch.float32, device=dev)
-    cls = torch.empty((B, Xo, Yo, Zo), dtype=torch.int64, device=dev)
-    _lib.launch('veon_occ_classify_grouped', dev, sem_low, _lib.strides(sem_low), K,
-                occ_eval._group_arg(group), int(n_merged), int(free_label), bin_low,
-                _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, merged, binv, cls)
-    return merged, binv, cls
+    return _launch_classify('veon_occ_classify_grouped', sem_low, bin_low, occ_size,
+                            int(n_merged),
+                            (occ_eval._group_arg(group), int(n_merged), int(free_label)))

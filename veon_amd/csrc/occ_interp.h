@@ -1,7 +1,7 @@
 // Trilinear sampling of the LOW-resolution occupancy volumes at evaluation-grid voxels:
 // source indices, corner offsets and the 8-corner blend, one definition each, shared by
-// the occupancy tail (occ_head.hip, occ_eval.hip: their labels agree bit for bit with each
-// other and with ATen; the library is built without FMA contraction) and by retrieval and
+// the occupancy tail (occ_tail.hip: the labels of its four kernels agree bit for bit with
+// each other and with ATen; the library is built without FMA contraction) and by retrieval and
 // the losses (occ_retrieval.hip, occ_align_loss.hip, occ_bin_loss.hip: a forward and a
 // backward that use it agree on every corner and weight).
 //
@@ -27,10 +27,17 @@ struct Axis {
   float l0, l1;
 };
 
+// The low-resolution and the evaluation grid with the scale of each axis: in / out in
+// float, as ATen's area_pixel_compute_scale without a scale_factor.
 struct Grid {
   int zi, yi, xi, Zo, Yo, Xo;
   float scz, scy, scx;
 };
+
+inline Grid grid_of(int zi, int yi, int xi, int Zo, int Yo, int Xo) {
+  return Grid{zi, yi, xi, Zo, Yo, Xo, (float)zi / (float)Zo, (float)yi / (float)Yo,
+              (float)xi / (float)Xo};
+}
 
 // Two source rules, on purpose.  `source` is ATen's, operation for operation: the tail's
 // labels must match ATen bit for bit.  `source_clamped` also clamps i0 at the top and l1

@@ -1,5 +1,5 @@
-// The tile walk of the label-only tails (occ_eval.hip: k_occ_labels; occ_classify_grouped.hip:
-// k_occ_labels_grouped): one definition of the mapping, the LDS staging of whole z columns,
+// The tile walk of the label-only tails (occ_tail.hip: k_occ_labels, k_occ_labels_grouped):
+// one definition of the mapping, the LDS staging of whole z columns,
 // the W-byte output and the LDS integer counters of the fused confusion matrix.  The two
 // kernels differ only in the label of a voxel, which they pass in as a functor.
 //
@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "host_common.h"
+#include "occ_interp.h"
 
 namespace {
 
@@ -37,11 +38,6 @@ template <> struct Bytes<1> { using T = uint8_t; };
 template <> struct Bytes<4> { using T = uint32_t; };
 template <> struct Bytes<8> { using T = uint2; };
 template <> struct Bytes<16> { using T = uint4; };
-
-struct Geometry {
-  int zi, yi, xi, Zo, Yo, Xo;
-  float scz, scy, scx;
-};
 
 __device__ __forceinline__ void zero_counters(unsigned* cnt, int n_cl) {
   for (int i = threadIdx.x; i < n_cl * n_cl; i += THREADS) cnt[i] = 0u;
@@ -60,7 +56,7 @@ __device__ __forceinline__ void flush_counters(const unsigned* cnt, int n_cl,
 // histogram is given.  `smem`: 16-byte aligned LDS of tile_lds_bytes().
 template <int W, typename Label>
 __device__ __forceinline__ void label_tiles(
-    unsigned char* smem, Label label, int n_cl, int B, const Geometry& g, int TY,
+    unsigned char* smem, Label label, int n_cl, int B, const Grid& g, int TY,
     uint8_t* __restrict__ labels, const uint8_t* __restrict__ gt,
     const uint8_t* __restrict__ mask, unsigned long long* __restrict__ hist) {
   using T = typename Bytes<W>::T;

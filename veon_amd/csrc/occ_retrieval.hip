@@ -8,7 +8,7 @@
 //
 // Here the upsampled volume is never formed: every point blends the 8 low-resolution
 // corner rows its output voxel interpolates from (the same ATen source-index rule as
-// occ_head.hip: src = scale*(dst+0.5)-0.5 clamped at 0, upper corner clamped at the
+// occ_tail.hip: src = scale*(dst+0.5)-0.5 clamped at 0, upper corner clamped at the
 // edge), so only the rows the points touch are read, from the channels-last half
 // rows of the sem head's PaddedVolume (interior only: never the halo or the guard
 // rows) or from an fp32 volume of any strides.

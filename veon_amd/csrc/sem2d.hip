@@ -27,6 +27,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "class_runs.h"
 #include "host_common.h"
 #include "lane_reduce.h"
 #include "occ_interp.h"
@@ -35,9 +36,6 @@ namespace {
 
 constexpr int THREADS = 256;
 constexpr int MAX_Q = 256;
-constexpr int MAX_ROWS = 256;     // K + 1 logit columns
-constexpr int MAX_MERGED = 64;
-constexpr unsigned RUN_ENDS = 0x80u;
 constexpr int TILE_W = 64;        // output columns of a tile: one per lane
 constexpr int WAVES = THREADS / 64;
 constexpr int TAB_FLOATS = 8192;  // LDS floats of the class table of one q chunk
@@ -131,11 +129,6 @@ __global__ __launch_bounds__(THREADS) void k_sem2d_ds(
     if (c0 + e < n) op[(int64_t)(c0 + e) * P] = acc[e];
 }
 
-// entry c: the merged channel of row c, | RUN_ENDS on the last row of its run
-struct GroupTable {
-  uint8_t e[MAX_ROWS];
-};
-
 struct FullArgs {
   const float* probs;   // (B,Q,K)
   const float* preds;   // (B,Q,h,w)
@@ -143,25 +136,6 @@ struct FullArgs {
   float scy, scx;       // h / H, w / W in float, as ATen
   int QC;               // proposals per LDS chunk
   int RCAP;             // LDS floats per proposal for the tile's source pixels; 0: none
-};
-
-// The running arg-max of the LABELS epilogue: rows arrive in order, a run of rows is merged
-// by its maximum (NaN sticks), the lowest merged channel that attains the maximum wins.
-struct ArgMax {
-  float vmax = -INFINITY, run = -INFINITY;
-  int cls = MAX_ROWS;
-  bool bad = false;
-  __device__ __forceinline__ void row(int chan, bool ends, float val) {
-    bad |= val != val;
-    run = run != run ? run : ((val != val || val > run) ? val : run);
-    if (ends) {
-      if (run > vmax || (run == vmax && chan < cls)) {
-        vmax = run;
-        cls = chan;
-      }
-      run = -INFINITY;
-    }
-  }
 };
 
 // One proposal onto the KACC sums of a lane's PIX pixels: sp is the proposal's source pixels
@@ -243,7 +217,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_sem2d_full(
   const int hw = a.h * a.w;
   const float* pb = a.preds + (int64_t)b * a.Q * hw;
   const float* tb = a.probs + (int64_t)b * a.Q * a.K;
-  ArgMax best[PIX];
+  RunArgMax best[PIX];   // (class_runs.h; MAX_ROWS there: the K + 1 logit columns)
   for (int k0 = 0; k0 < a.K; k0 += KACC) {
     const int kc = min(KACC, a.K - k0);
     float acc[PIX][KACC];
@@ -308,25 +282,6 @@ __global__ __launch_bounds__(THREADS, 2) void k_sem2d_full(
             (uint8_t)(best[j].bad || best[j].cls >= MAX_ROWS ? ignore_label : best[j].cls);
     }
   }
-}
-
-// group (HOST, K bytes) -> the kernel's table; false unless every row's channel is below
-// n_merged, the rows of a channel are consecutive and every channel has exactly one run
-bool make_table(const uint8_t* group, int K, int n_merged, GroupTable* table) {
-  bool used[MAX_MERGED] = {};
-  int runs = 0;
-  for (int c = 0; c < MAX_ROWS; ++c) table->e[c] = 0;
-  for (int c = 0; c < K; ++c) {
-    if (group[c] >= n_merged) return false;
-    const bool ends = c + 1 == K || group[c + 1] != group[c];
-    table->e[c] = (uint8_t)(group[c] | (ends ? RUN_ENDS : 0u));
-    if (ends) {
-      if (used[group[c]]) return false;
-      used[group[c]] = true;
-      ++runs;
-    }
-  }
-  return runs == n_merged;
 }
 
 bool shape_ok(int B, int Q, int K, int h, int w) {

@@ -29,18 +29,7 @@ from ...align_loss import voxel_cosine
 from ...align_select import select_entries
 from ...occ_bin_loss import bin_occ_loss
 from ...retrieval import retrieve_points
-
-
-def _groups(class_reflection, device):
-    """Group id of every 2-D class: consecutive equal values of ``class_reflection``
-    form one merged class (numbered in order of appearance) -> ((K2,) long, count)."""
-    ref = [int(v) for v in class_reflection]
-    gid, cur = [], -1
-    for i, v in enumerate(ref):
-        if i == 0 or v != ref[i - 1]:
-            cur += 1
-        gid.append(cur)
-    return torch.tensor(gid, dtype=torch.long, device=device), cur + 1
+from ...vocabulary import group_ids
 
 
 def _merged_argmax(values, gid, n_groups):
@@ -149,7 +138,8 @@ class Proj2Dto3DLoss(nn.Module):
         Zo, Yo, Xo = occ_size
         table = ov_classifier_weight.detach().to(dtype)
         priority = self.priority.to(device=device, dtype=dtype)
-        gid, n_groups = _groups(class_reflection, device)
+        gid, n_groups = group_ids(class_reflection)
+        gid = torch.tensor(gid, dtype=torch.long, device=device)
         assert gid.shape[0] == sem_seg_2d.shape[2] and n_groups == class_num
         height, width = img_inputs[0].shape[-2:]
         pts = self._project(img_inputs, occ_size, dtype, device)

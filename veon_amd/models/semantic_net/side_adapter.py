@@ -420,7 +420,7 @@ def semantic_branch_2d(side_net, rec_head, ov_classifier_weight, images, clip_fe
     below.  Then ``full=False`` leaves ``sem_seg`` out (a training step reads only
     ``sem_seg_ds``) and ``labels=True`` adds ``labels_2d``, uint8 (B*N,H,W): the arg-max of
     ``sem_seg``, over the runs of rows of ``group`` / ``n_merged``
-    (``occ_eval.group_table``) when a detailed vocabulary is set."""
+    (``vocabulary.group_table``) when a detailed vocabulary is set."""
     mask_preds, attn_biases, san_feats = side_net(images, clip_feats)
     mask_embs = [rec_head(clip_feats, ab, normalize=True) for ab in attn_biases]
     mask_logits = [torch.einsum('bqc,nc->bqn', e, ov_classifier_weight) for e in mask_embs]

@@ -148,8 +148,7 @@ class VeonOccupancyPath(nn.Module):
         hipGraph captured from the path before the call still holds the old rows and must
         be captured again (``CameraShardedStep`` refuses to replay).  A path on which this
         is never called is unchanged in every output and bit."""
-        from ..align_select import group_ids
-        from ..occ_eval import group_table
+        from ..vocabulary import group_ids, group_table
         from ._native_cache import invalidate_all
         vocabulary = list(vocabulary)
         if len(class_reflection) != len(vocabulary):
@@ -356,57 +355,39 @@ class VeonOccupancyPath(nn.Module):
         extra = {'feat_low': feat, 'bin_low': bin_occ} if return_features else {}
         if count is not None and not labels_only:
             raise ValueError('count needs labels_only=True')
+        gt, mask, hist = count or (None, None, None)
         native = bin_occ.is_cuda and not torch.is_grad_enabled() and bin_occ.shape[1] == 2
         ov = self.__dict__['_ov']
-        if ov is not None:
-            merge = (ov['group'], ov['n_merged'], ov['free_label'])
+        merge = () if ov is None else (ov['group'], ov['n_merged'], ov['free_label'])
+        # the label tails count by themselves: natively, and (grouped) as the CPU's mirror
+        if labels_only and (native or (ov is not None and not bin_occ.is_cuda)):
             low = classifier_logits_low(W, feat).float()
-            gt, mask, hist = count or (None, None, None)
-            if labels_only and (native or not bin_occ.is_cuda):
-                # (on the CPU the wrapper itself is the torch mirror)
-                occ = occ_eval.occ_labels_grouped(low, bin_occ.float(), self.occ_size,
-                                                  *merge, gt, mask, hist)
-                return {'occ_pred_cls': occ, **extra}
-            if native:
-                sem_occ, bin_up, occ = conv3d_ops.occ_classify_grouped(
-                    low, bin_occ.float(), self.occ_size, *merge)
-            else:
-                sem_occ, bin_up, occ = occ_eval.occ_grouped_reference(
-                    low, bin_occ, self.occ_size, *merge)
-            if labels_only:     # a device forward with grad enabled
-                occ = occ.to(torch.uint8)
-                if count is not None:
-                    occ_eval.confusion(occ, gt, mask, hist.shape[0], hist)
-                return {'occ_pred_cls': occ, **extra}
-            return {'bin_occ': bin_up, 'sem_occ': sem_occ, 'occ_pred_cls': occ, **extra}
-        if native and labels_only:
-            # the same labels, and nothing but the labels, from one kernel
-            low = classifier_logits_low(W, feat)
-            gt, mask, hist = count or (None, None, None)
-            occ = occ_eval.occ_labels(low.float(), bin_occ.float(), self.occ_size, gt,
-                                      mask, hist)
+            tail = occ_eval.occ_labels if ov is None else occ_eval.occ_labels_grouped
+            occ = tail(low, bin_occ.float(), self.occ_size, *merge, gt, mask, hist)
             return {'occ_pred_cls': occ, **extra}
         if native:
             # upsampling x2, both softmaxes, arg-max and the label volume: one kernel
-            low = classifier_logits_low(W, feat)
-            sem_occ, bin_up, occ = conv3d_ops.occ_classify(low.float(), bin_occ.float(),
-                                                           self.occ_size)
-            return {'bin_occ': bin_up, 'sem_occ': sem_occ, 'occ_pred_cls': occ, **extra}
-        sem_occ = semantic_inference_3d_fused(W, feat, self.occ_size)
-        bin_occ = F.interpolate(bin_occ, size=tuple(self.occ_size), mode='trilinear',
-                                align_corners=False)
-        # veon_temporal.py:219-227
-        score, cls = torch.softmax(sem_occ, dim=1).max(dim=1)
-        keep = (score > 0.0) & (torch.softmax(bin_occ, dim=1)[:, 0] > 0.5)
-        occ = torch.where(keep, cls, torch.full_like(cls, sem_occ.shape[1]))
-        occ = occ.permute(0, 3, 2, 1).contiguous()
-        if labels_only:
-            occ = occ.to(torch.uint8)
-            if count is not None:
-                gt, mask, hist = count
-                occ_eval.confusion(occ, gt, mask, hist.shape[0], hist)
-            return {'occ_pred_cls': occ, **extra}
-        return {'bin_occ': bin_occ, 'sem_occ': sem_occ, 'occ_pred_cls': occ, **extra}
+            low = classifier_logits_low(W, feat).float()
+            tail = conv3d_ops.occ_classify if ov is None else conv3d_ops.occ_classify_grouped
+            sem_occ, bin_occ, occ = tail(low, bin_occ.float(), self.occ_size, *merge)
+        elif ov is not None:
+            sem_occ, bin_occ, occ = occ_eval.occ_grouped_reference(
+                classifier_logits_low(W, feat).float(), bin_occ, self.occ_size, *merge)
+        else:
+            sem_occ = semantic_inference_3d_fused(W, feat, self.occ_size)
+            bin_occ = F.interpolate(bin_occ, size=tuple(self.occ_size), mode='trilinear',
+                                    align_corners=False)
+            # veon_temporal.py:219-227
+            score, cls = torch.softmax(sem_occ, dim=1).max(dim=1)
+            keep = (score > 0.0) & (torch.softmax(bin_occ, dim=1)[:, 0] > 0.5)
+            occ = torch.where(keep, cls, torch.full_like(cls, sem_occ.shape[1]))
+            occ = occ.permute(0, 3, 2, 1).contiguous()
+        if not labels_only:
+            return {'bin_occ': bin_occ, 'sem_occ': sem_occ, 'occ_pred_cls': occ, **extra}
+        occ = occ.to(torch.uint8)     # a forward with grad enabled, or without a vocabulary
+        if count is not None:         # on the CPU
+            occ_eval.confusion(occ, gt, mask, hist.shape[0], hist)
+        return {'occ_pred_cls': occ, **extra}
 
     def lift_cameras(self, images, img_metas, lo, hi, depth=None):
         """The UN-POOLED lifted volume (B, C, Z, Y, X) fp32 of cameras [lo, hi) of

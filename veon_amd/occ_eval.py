@@ -3,11 +3,11 @@ mIoU of ``Metric_mIoU`` (mmdet3d/datasets/occ_metrics.py:52-147), which is the o
 ``NuScenesDatasetOccpancy.evaluate`` computes, and the F-score of ``Metric_FScore``
 (occ_metrics.py:150-237), the geometry metric of the Occ3D benchmark.
 
-    occ_labels   the label-only tail of the occupancy path (csrc/occ_eval.hip): uint8
+    occ_labels   the label-only tail of the occupancy path (csrc/occ_tail.hip): uint8
                  labels as ``VEONTemporal.simple_test`` returns them, nothing else
                  written; optionally the confusion matrix in the same kernel
     occ_labels_grouped  the same against a detailed vocabulary: K logit rows, runs of
-                 rows merged by their maximum (csrc/occ_classify_grouped.hip; a torch
+                 rows merged by their maximum (csrc/occ_tail.hip; a torch
                  mirror on the CPU)
     confusion    the same confusion matrix for labels that already exist
     OccMiouMetric  ``Metric_mIoU`` with its state (an int64 histogram) on the device:
@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .vocabulary import group_table, lowest_argmax, merge_runs
 
 # occ_metrics.py:59-62
 CLASS_NAMES = ['others', 'barrier', 'bicycle', 'bus', 'car', 'construction_vehicle',
@@ -46,6 +47,30 @@ def _as_u8(t, what):
     return t
 
 
+def _check_counting(gt, mask, hist, shape, n_cl):
+    """The optional arguments of the label tails: ``gt`` / ``mask`` uint8 of ``shape`` =
+    (B, X, Y, Z), ``hist`` int64 with n_cl * n_cl elements."""
+    for name, t in (('gt', gt), ('mask', mask)):
+        if t is not None:
+            _as_u8(t, name)
+            assert tuple(t.shape) == shape, (name, tuple(t.shape))
+    if hist is not None:
+        assert hist.dtype == torch.int64 and hist.is_contiguous()
+        assert hist.numel() == n_cl * n_cl, (tuple(hist.shape), n_cl)
+
+
+def _launch_labels(entry, dev, sem_low, bin_low, occ_size, table, gt, mask, hist):
+    """uint8 (B,X,Y,Z) from ``entry``; ``table``: the arguments between the row count and
+    ``bin_low`` (none, or the group table's three)."""
+    assert sem_low.dtype == bin_low.dtype == torch.float32
+    B, K, zi, yi, xi = sem_low.shape
+    Zo, Yo, Xo = (int(v) for v in occ_size)
+    labels = torch.empty((B, Xo, Yo, Zo), dtype=torch.uint8, device=dev)
+    _lib.launch(entry, dev, sem_low, _lib.strides(sem_low), K, *table, bin_low,
+                _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, labels, gt, mask, hist)
+    return labels
+
+
 def occ_labels(sem_low, bin_low, occ_size, gt=None, mask=None, hist=None):
     """Label volume (B,X,Y,Z) uint8 of the class logits ``sem_low`` (B,Q,z,y,x) and the
     occupancy logits ``bin_low`` (B,2,z,y,x) -- fp32, ANY strides -- at ``occ_size`` =
@@ -58,17 +83,9 @@ def occ_labels(sem_low, bin_low, occ_size, gt=None, mask=None, hist=None):
     B, Q, zi, yi, xi = sem_low.shape
     assert tuple(bin_low.shape) == (B, 2, zi, yi, xi)
     Zo, Yo, Xo = (int(v) for v in occ_size)
-    for name, t in (('gt', gt), ('mask', mask)):
-        if t is not None:
-            _as_u8(t, name)
-            assert tuple(t.shape) == (B, Xo, Yo, Zo), (name, tuple(t.shape))
-    if hist is not None:
-        assert hist.dtype == torch.int64 and hist.is_contiguous()
-        assert hist.numel() == (Q + 1) * (Q + 1), (tuple(hist.shape), Q)
-    labels = torch.empty((B, Xo, Yo, Zo), dtype=torch.uint8, device=dev)
-    _lib.launch('veon_occ_labels', dev, sem_low, _lib.strides(sem_low), Q, bin_low,
-                _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, labels, gt, mask, hist)
-    return labels
+    _check_counting(gt, mask, hist, (B, Xo, Yo, Zo), Q + 1)
+    return _launch_labels('veon_occ_labels', dev, sem_low, bin_low, occ_size, (), gt, mask,
+                          hist)
 
 
 def confusion(pred, gt, mask=None, n_cl=18, hist=None, flag=None):
@@ -115,46 +132,6 @@ def confusion(pred, gt, mask=None, n_cl=18, hist=None, flag=None):
 
 
 # ------------------------------------------------------------- detailed vocabulary
-MAX_ROWS = 256       # logit rows of the grouped tails
-MAX_MERGED = 64      # merged channels
-
-
-def group_table(group, n_merged, free_label, K=None, with_hist=False):
-    """The checked group table of the grouped tails as a list of ints: ``group[c]`` is
-    the merged channel of logit row c.  ValueError unless 1 <= K <= 256, 1 <= n_merged
-    <= 64, every entry is in [0, n_merged), the rows of a channel are consecutive (no
-    split runs), no channel is used by two runs and every channel is used, and 0 <=
-    free_label <= 255 (<= 63 with a histogram, whose side is max(n_merged, free_label +
-    1))."""
-    group = [int(v) for v in group]
-    n_merged, free_label = int(n_merged), int(free_label)
-    if K is not None and len(group) != K:
-        raise ValueError('the group table has %d entries for %d logit rows' % (len(group), K))
-    if not 1 <= len(group) <= MAX_ROWS:
-        raise ValueError('the grouped tail takes 1 to %d logit rows, got %d'
-                         % (MAX_ROWS, len(group)))
-    if not 1 <= n_merged <= MAX_MERGED:
-        raise ValueError('n_merged must be in [1, %d], got %d' % (MAX_MERGED, n_merged))
-    if not 0 <= free_label <= 255:
-        raise ValueError('free_label must be in [0, 255], got %d' % free_label)
-    if with_hist and max(n_merged, free_label + 1) > MAX_MERGED:
-        raise ValueError('the histogram holds at most %d classes, free_label is %d'
-                         % (MAX_MERGED, free_label))
-    seen = set()
-    for c, ch in enumerate(group):
-        if not 0 <= ch < n_merged:
-            raise ValueError('row %d names merged channel %d of %d' % (c, ch, n_merged))
-        if c == 0 or ch != group[c - 1]:
-            if ch in seen:
-                raise ValueError('merged channel %d is used by two runs of rows (a split '
-                                 'run, or a channel used twice)' % ch)
-            seen.add(ch)
-    if len(seen) != n_merged:
-        raise ValueError('%d of the %d merged channels have no row' %
-                         (n_merged - len(seen), n_merged))
-    return group
-
-
 def _group_arg(group):
     return _lib.host_array(group, ctypes.c_uint8)
 
@@ -171,18 +148,8 @@ def occ_grouped_reference(sem_low, bin_low, occ_size, group, n_merged, free_labe
     size = tuple(int(v) for v in occ_size)
     up = F.interpolate(sem_low.float(), size=size, mode='trilinear', align_corners=False)
     bin_up = F.interpolate(bin_low.float(), size=size, mode='trilinear', align_corners=False)
-    merged = [None] * n_merged
-    left = 0
-    while left < len(group):
-        right = left
-        while right + 1 < len(group) and group[right + 1] == group[left]:
-            right += 1
-        merged[group[left]] = torch.max(up[:, left:right + 1], dim=1).values
-        left = right + 1
-    merged = torch.stack(merged, dim=1)
-    top = merged.max(dim=1, keepdim=True).values
-    index = torch.arange(n_merged, device=up.device).view(1, -1, 1, 1, 1)
-    cls = torch.where(merged == top, index, torch.full_like(index, n_merged)).amin(dim=1)
+    merged = merge_runs(up, group, n_merged)
+    cls, top = lowest_argmax(merged)
     scored = ~torch.isnan(up).any(dim=1) & torch.isfinite(top[:, 0])
     keep = scored & (torch.softmax(bin_up, dim=1)[:, 0] > 0.5)
     labels = torch.where(keep, cls, torch.full_like(cls, free_label))
@@ -208,13 +175,7 @@ def occ_labels_grouped(sem_low, bin_low, occ_size, group, n_merged, free_label, 
     Zo, Yo, Xo = (int(v) for v in occ_size)
     if (gt is None) != (hist is None) or (mask is not None and gt is None):
         raise ValueError('gt and hist are given together; a mask needs both')
-    for name, t in (('gt', gt), ('mask', mask)):
-        if t is not None:
-            _as_u8(t, name)
-            assert tuple(t.shape) == (B, Xo, Yo, Zo), (name, tuple(t.shape))
-    if hist is not None:
-        assert hist.dtype == torch.int64 and hist.is_contiguous()
-        assert hist.numel() == n_cl * n_cl, (tuple(hist.shape), n_cl)
+    _check_counting(gt, mask, hist, (B, Xo, Yo, Zo), n_cl)
     if not sem_low.is_cuda:
         labels = occ_grouped_reference(sem_low, bin_low, occ_size, group, n_merged,
                                        free_label)[2].to(torch.uint8)
@@ -222,12 +183,8 @@ def occ_labels_grouped(sem_low, bin_low, occ_size, group, n_merged, free_label, 
             confusion(labels, gt, mask, n_cl, hist)
         return labels
     dev = _lib.require_device(sem_low, bin_low, gt, mask, hist)
-    assert sem_low.dtype == bin_low.dtype == torch.float32
-    labels = torch.empty((B, Xo, Yo, Zo), dtype=torch.uint8, device=dev)
-    _lib.launch('veon_occ_labels_grouped', dev, sem_low, _lib.strides(sem_low), K,
-                _group_arg(group), int(n_merged), int(free_label), bin_low,
-                _lib.strides(bin_low), B, zi, yi, xi, Zo, Yo, Xo, labels, gt, mask, hist)
-    return labels
+    return _launch_labels('veon_occ_labels_grouped', dev, sem_low, bin_low, occ_size,
+                          (_group_arg(group), int(n_merged), int(free_label)), gt, mask, hist)
 
 
 def _default_device(device):

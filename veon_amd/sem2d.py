@@ -22,7 +22,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .occ_eval import _group_arg, group_table
+from .occ_eval import _group_arg
+from .vocabulary import group_table, lowest_argmax, merge_runs as merge_runs_torch
 
 MAX_Q = 256
 MAX_COLUMNS = 256     # K + 1
@@ -46,32 +47,12 @@ def semantic_map_torch(mask_logits, mask_preds, size):
                         up.sigmoid())
 
 
-def merge_runs_torch(sem, group, n_merged):
-    """(B,K,H,W) -> (B,n_merged,H,W): the maximum over each run of rows of ``group``
-    (``torch.max``: NaN propagates)."""
-    merged = [None] * n_merged
-    left = 0
-    while left < len(group):
-        right = left
-        while right + 1 < len(group) and group[right + 1] == group[left]:
-            right += 1
-        merged[group[left]] = torch.max(sem[:, left:right + 1], dim=1).values
-        left = right + 1
-    return torch.stack(merged, dim=1)
-
-
 def labels_of_map(sem, group=None, n_merged=None, ignore_label=255):
     """uint8 (B,H,W) of a semantic map (B,K,H,W): runs of rows merged by their maximum,
     the lowest (merged) channel that attains the maximum, ``ignore_label`` where any row
     is NaN."""
-    if group is not None:
-        merged = merge_runs_torch(sem, group, n_merged)
-    else:
-        merged = sem
-    n = merged.shape[1]
-    top = merged.max(dim=1, keepdim=True).values
-    index = torch.arange(n, device=sem.device).view(1, -1, 1, 1)
-    cls = torch.where(merged == top, index, torch.full_like(index, n)).amin(dim=1)
+    cls, _ = lowest_argmax(sem if group is None else merge_runs_torch(sem, group,
+                                                                       n_merged))
     bad = torch.isnan(sem).any(dim=1)
     return torch.where(bad, torch.full_like(cls, ignore_label), cls).to(torch.uint8)
 
@@ -174,7 +155,7 @@ def semantic_map(mask_logits, mask_preds, size):
 def semantic_labels(mask_logits, mask_preds, size, group=None, n_merged=None,
                     ignore_label=255):
     """-> uint8 labels (B,H,W): the arg-max over the rows of ``semantic_map`` (the same
-    values bit for bit, never written).  ``group`` (K ints, ``occ_eval.group_table``; with
+    values bit for bit, never written).  ``group`` (K ints, ``vocabulary.group_table``; with
     ``n_merged``): the merged channel of every row -- each run of rows is merged by its
     maximum and the label is the merged channel.  The lowest channel that attains the
     maximum wins; a pixel with a NaN in any row gets ``ignore_label``."""

@@ -7,7 +7,87 @@ The reference classifies against the DETAILED descriptions of its vocabulary ("c
 (``class_reflection``) and merges the descriptions of one class by their maximum
 (``occ_eval.occ_labels_grouped``).  The category lists themselves are data of the
 caller: this package holds none.
+
+The merge rule has one home here, for the kernels' wrappers and their torch mirrors alike:
+``group_ids`` (runs of ``class_reflection`` -> merged classes), ``group_table`` (the
+checked table the grouped tails take), ``merge_runs`` (the maximum over each run of rows)
+and ``lowest_argmax`` (the tie-break).
 """
+import torch
+
+MAX_ROWS = 256       # logit rows of the grouped tails
+MAX_MERGED = 64      # merged channels
+
+
+def group_ids(class_reflection):
+    """Merged class of every 2-D class: consecutive equal values of ``class_reflection``
+    form one merged class, numbered in order of appearance -> (list, count)."""
+    ref = [int(v) for v in class_reflection]
+    gid, cur = [], -1
+    for i, v in enumerate(ref):
+        if i == 0 or v != ref[i - 1]:
+            cur += 1
+        gid.append(cur)
+    return gid, cur + 1
+
+
+def group_table(group, n_merged, free_label, K=None, with_hist=False):
+    """The checked group table of the grouped tails as a list of ints: ``group[c]`` is
+    the merged channel of logit row c.  ValueError unless 1 <= K <= 256, 1 <= n_merged
+    <= 64, every entry is in [0, n_merged), the rows of a channel are consecutive (no
+    split runs), no channel is used by two runs and every channel is used, and 0 <=
+    free_label <= 255 (<= 63 with a histogram, whose side is max(n_merged, free_label +
+    1))."""
+    group = [int(v) for v in group]
+    n_merged, free_label = int(n_merged), int(free_label)
+    if K is not None and len(group) != K:
+        raise ValueError('the group table has %d entries for %d logit rows' % (len(group), K))
+    if not 1 <= len(group) <= MAX_ROWS:
+        raise ValueError('the grouped tail takes 1 to %d logit rows, got %d'
+                         % (MAX_ROWS, len(group)))
+    if not 1 <= n_merged <= MAX_MERGED:
+        raise ValueError('n_merged must be in [1, %d], got %d' % (MAX_MERGED, n_merged))
+    if not 0 <= free_label <= 255:
+        raise ValueError('free_label must be in [0, 255], got %d' % free_label)
+    if with_hist and max(n_merged, free_label + 1) > MAX_MERGED:
+        raise ValueError('the histogram holds at most %d classes, free_label is %d'
+                         % (MAX_MERGED, free_label))
+    seen = set()
+    for c, ch in enumerate(group):
+        if not 0 <= ch < n_merged:
+            raise ValueError('row %d names merged channel %d of %d' % (c, ch, n_merged))
+        if c == 0 or ch != group[c - 1]:
+            if ch in seen:
+                raise ValueError('merged channel %d is used by two runs of rows (a split '
+                                 'run, or a channel used twice)' % ch)
+            seen.add(ch)
+    if len(seen) != n_merged:
+        raise ValueError('%d of the %d merged channels have no row' %
+                         (n_merged - len(seen), n_merged))
+    return group
+
+
+def merge_runs(t, group, n_merged):
+    """(B, K, ...) -> (B, n_merged, ...): the maximum over each run of rows of ``group``
+    (``torch.max``: NaN propagates)."""
+    merged = [None] * n_merged
+    left = 0
+    while left < len(group):
+        right = left
+        while right + 1 < len(group) and group[right + 1] == group[left]:
+            right += 1
+        merged[group[left]] = torch.max(t[:, left:right + 1], dim=1).values
+        left = right + 1
+    return torch.stack(merged, dim=1)
+
+
+def lowest_argmax(merged):
+    """(B, n, ...) -> ((B, ...) int64, (B, 1, ...)): the lowest channel that attains the
+    maximum over dim 1 (n where none does: a NaN among them), and that maximum."""
+    n = merged.shape[1]
+    top = merged.max(dim=1, keepdim=True).values
+    index = torch.arange(n, device=merged.device).view((1, n) + (1,) * (merged.dim() - 2))
+    return torch.where(merged == top, index, torch.full_like(index, n)).amin(dim=1), top
 
 
 def build_vocabulary(words, categories):
