@@ -120,6 +120,23 @@ def declared_symbols():
     return sorted(_SIGNATURES)
 
 
+# Entry points declared outside veon_hip.h (include/ext/*.h, the same style): bound beside
+# _SIGNATURES and exported by the same libraries, but not part of ``declared_symbols()``,
+# over which the launch ledger of the tests closes.
+EXT_HEADERS = (os.path.join(INCLUDE, 'ext', 'veon_hip_query.h'),)
+_EXT_SIGNATURES = {}
+for _path in EXT_HEADERS:
+    for _name, _sig in _parse_header(_path).items():
+        if _name in _SIGNATURES or _name in _EXT_SIGNATURES:
+            raise VeonHipError('%s: %s is declared twice' % (_path, _name))
+        _EXT_SIGNATURES[_name] = _sig
+
+
+def ext_symbols():
+    """Every entry point the headers under include/ext/ declare."""
+    return sorted(_EXT_SIGNATURES)
+
+
 def lib():
     """The native library of the process's half flavour (veon_amd/half.py):
     libveon_hip.so (bf16 operands) or libveon_hip_f16.so (fp16), the same entry
@@ -133,7 +150,8 @@ def lib():
                 'veon_amd: %s not found -- build it with `python -m veon_amd.build` '
                 '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % path)
         loaded = ctypes.CDLL(path)
-        for name, (restype, argtypes) in _SIGNATURES.items():
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + \
+                list(_EXT_SIGNATURES.items()):
             fn = getattr(loaded, name)
             fn.restype, fn.argtypes = restype, argtypes
         if loaded.veon_half_mode() != (1 if flavour == 'fp16' else 0):

@@ -32,7 +32,8 @@ def sources():
 
 
 def _headers():
-    return glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(INCLUDE, '*.h'))
+    return glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(INCLUDE, '*.h')) + \
+        glob.glob(os.path.join(INCLUDE, 'ext', '*.h'))
 
 
 def _deps():

@@ -18,7 +18,7 @@ no vectors for it; tests compare against ``torch.nn.MultiheadAttention``
 semantics.  What the reference itself owns around the block IS pinned by vectors
 generated from its unmodified files (oracle/tools/gen_golden_clip_*.py): the
 query-token cross attention with the extra "self" logit (attn_helper.py:34-300,
-PyTorch here: 100 queries are not a hot loop), the trunk wiring
+PyTorch here; natively with ``ClipRecHead.hip_query``), the trunk wiring
 (``FeatureExtractor``) and the recognition head (``RecWithAttnbiasHead``).
 """
 from collections import OrderedDict
@@ -157,7 +157,8 @@ def cross_attn_with_self_bias(attn, query, key, value, attn_mask=None):
     addition, over THEMSELVES through one extra logit q.k_self whose value is
     the query's own v projection -- a softmax over L + 1 logits per query.
     ``attn`` is an nn.MultiheadAttention holding the packed projections.
-    PyTorch implementation (100 queries: not a hot loop)."""
+    PyTorch implementation; ``ClipRecHead.hip_query`` runs the same arithmetic on the
+    library (``vit_ops.query_attention``)."""
     K, N, D = query.shape
     L = key.shape[0]
     H = attn.num_heads
@@ -446,9 +447,17 @@ class ClipRecHead(NativeCacheMixin, nn.Module):
 
     ``features`` / ``clip_outputs``: dict with ``[i]`` = (N,C,h,w) patch map and
     ``['%d_cls_token' % i]`` = (1,N,C), as ``ClipOutput`` in the reference.
+
+    ``hip_query`` (class attribute, default False; ``forward(hip_query=...)`` overrides it
+    for one call): opt-in native query path.  When set, and ``_hip_query_ok`` holds (a ROCm
+    device, no autograd, every block in eval mode, fp32 tokens, D % 64 == 0, head_dim 64),
+    ``forward`` runs the SOS/query tokens batch-major on the library, nine launches per
+    tail block (``_native_queries``) and no fp32 projection; ``ln_post``, ``proj`` and
+    ``normalize`` stay in torch.  Anything else takes ``cross_attn_layer`` unchanged.
     """
 
     _native_cache = {'_hip_cache': dict}
+    hip_query = False
 
     def __init__(self, resblocks, ln_post, proj, first_layer_idx=0,
                  sos_token_format='cls_token', sos_token_num=1,
@@ -482,7 +491,9 @@ class ClipRecHead(NativeCacheMixin, nn.Module):
         for ab in attn_biases:
             n, num_head, num_sos, h, w = ab.shape
             ab = ab.reshape(n, num_head * num_sos, h, w)
-            if self.downsample_method in ('bicubic', 'bilinear', 'nearest'):
+            if (h, w) == tuple(target_shape):
+                pass        # already at the target grid (MLPMaskDecoder.attn_bias_at)
+            elif self.downsample_method in ('bicubic', 'bilinear', 'nearest'):
                 ab = interpolate(ab, size=target_shape, mode=self.downsample_method,
                                  align_corners=False)
             elif self.downsample_method == 'avg':
@@ -498,7 +509,53 @@ class ClipRecHead(NativeCacheMixin, nn.Module):
             out = [out[0] for _ in self.resblocks]
         return out
 
-    def forward(self, features, attn_bias, normalize=False, clip_outputs=None):
+    def _hip_query_ok(self, x):
+        """The native query path's own test (the switch is read by ``forward``): the
+        condition of ``run_blocks``' MFMA path over ALL tail blocks, on fp32 tokens."""
+        blocks = list(self.resblocks)
+        return (bool(blocks) and x.dtype == torch.float32
+                and hip_blocks_ok(blocks, x, x.shape[-1]))
+
+    def _native_queries(self, blocks, sos, xs, biases):
+        """``cross_attn_layer`` over the tail blocks on the library: sos (K, N, D) fp32 query
+        tokens, xs[i] (L, N, D) the memory of block i, biases[i] (N*heads, K, L - 1) float
+        or bool -> (K, N, D), a view of a batch-major stream.  Per block: LayerNorm and the
+        K/V half of the packed projection over the memory rows (the q rows of the weight
+        are skipped: a contiguous row slice), LayerNorm and the whole projection over the
+        query rows, ``veon_query_attention`` (key0 = 1: the patch tokens only, exp2
+        domain), out_proj onto the stream, LayerNorm, fc1 + activation, fc2 onto the
+        stream."""
+        K, N, D = sos.shape
+        s = torch.empty((N, K, D), dtype=torch.float32, device=sos.device)
+        s.copy_(sos.permute(1, 0, 2))         # a private stream: updated in place
+        s = s.view(N * K, D)
+        for i, blk in enumerate(blocks):
+            w = self._hip_cache.get(id(blk))
+            if w is None:
+                w = self._hip_cache[id(blk)] = _HipClipWeights(blk)
+            H = w.heads
+            # run_blocks' native snapshots are batch-major already: no copy then
+            mem = xs[i].permute(1, 0, 2).contiguous()
+            L = mem.shape[1]
+            hm = vit_ops.layernorm(mem.view(N * L, D), *w.n1)
+            mem_kv = vit_ops.linear(hm, w.w_qkv[D:], w.b_qkv[D:]).view(N, L, 2, H, 64)
+            hq = vit_ops.layernorm(s, *w.n1)
+            q_qkv = vit_ops.linear(hq, w.w_qkv, w.b_qkv).view(N, K, 3, H, 64)
+            b = biases[i]
+            if b is not None:
+                if b.dtype == torch.bool:
+                    b = torch.zeros(b.shape, dtype=torch.float32, device=b.device) \
+                        .masked_fill_(b, float('-inf'))
+                b = b.float().reshape(N, H, K, L - 1)
+            o = vit_ops.query_attention(q_qkv, mem_kv, H, b, key0=1, q_log2=True)
+            vit_ops.linear_residual_(s, o.view(N * K, D), w.w_proj, w.b_proj)
+            h2 = vit_ops.layernorm(s, *w.n2)
+            u = vit_ops.linear(h2, w.w_fc1, w.b_fc1, epilogue=w.act)
+            vit_ops.linear_residual_(s, u, w.w_fc2, w.b_fc2)
+        return s.view(N, K, D).permute(1, 0, 2)
+
+    def forward(self, features, attn_bias, normalize=False, clip_outputs=None,
+                hip_query=None):
         k0 = self.first_layer_idx
         cls_token = features['%d_cls_token' % k0]        # 1,n,c
         pix = features[k0]                               # n,c,h,w
@@ -516,8 +573,13 @@ class ClipRecHead(NativeCacheMixin, nn.Module):
         # output is saved): all at once, on the MFMA kernels where run_blocks can
         run = blocks if clip_outputs is not None else blocks[:-1]
         xs = [x] + (run_blocks(run, x, None, self._hip_cache) if run else [])
+        native = (self.hip_query if hip_query is None else hip_query) \
+            and self._hip_query_ok(x)
+        if native:
+            sos = self._native_queries(blocks, sos, xs, biases)
         for i, blk in enumerate(blocks):
-            sos = cross_attn_layer(blk, sos, xs[i][1:], biases[i])
+            if not native:
+                sos = cross_attn_layer(blk, sos, xs[i][1:], biases[i])
             if clip_outputs is not None:
                 self._save(clip_outputs, i + k0 + 1, xs[i + 1], (h, w))
         sos = self.ln_post(sos.permute(1, 0, 2))

@@ -241,11 +241,62 @@ class MLPMaskDecoder(nn.Module):
                             affine_func=dense)
         self.bias_scaling = nn.Linear(1, 1) if rescale_attn_bias else nn.Identity()
 
-    def forward(self, query, x):
+    BIAS_AT_MODES = ('bilinear', 'bicubic', 'avg')
+
+    def bias_at_ok(self, mode):
+        """``attn_bias_at`` covers this decoder and this resize: a LINEAR resize whose
+        weights sum to one, and one bias layer."""
+        return mode in self.BIAS_AT_MODES and self.total_layers == 1
+
+    def attn_bias_at(self, query, x, size, mode, query_embed=None):
+        """The attention bias of ``forward`` resized to ``size`` = (h, w) by ``mode`` (the
+        recognition head's ``downsample_method``), (B, heads, Q, h, w), without forming it
+        at the source grid.  The resize is linear with weights that sum to one, so resizing
+        the product equals the product with the resized factor: with ``hid`` the
+        ``attn_mlp`` output before its last layer (W3, b3) and q' = query_mlp(query),
+
+          bias[b,n,q,p] = s (sum_k (sum_c q'[b,q,c] W3[n,c,k]) resize(hid)[b,k,p]
+                             + sum_c q'[b,q,c] b3[n,c]) + t,
+
+        (s, t) the ``bias_scaling`` Linear(1, 1) or (1, 0): three small matmuls and one
+        resize of ``mlp_channels`` maps, instead of a 1x1 conv to heads * c channels, a
+        batched matmul at the source grid and a resize of B * heads * Q maps.
+        ``query_embed``: q' when the caller has it already."""
+        if not self.bias_at_ok(mode):
+            raise ValueError('attn_bias_at: mode %r with %d bias layers takes forward\'s '
+                             'route' % (mode, self.total_layers))
+        qe = self.query_mlp(query) if query_embed is None else query_embed    # (B, Q, c)
+        hid = x
+        for layer in self.attn_mlp.layers[:-1]:
+            hid = F.relu(layer(hid))
+        if tuple(hid.shape[-2:]) != tuple(size):
+            if mode == 'avg':
+                hid = F.adaptive_avg_pool2d(hid, output_size=size)
+            else:
+                hid = interpolate(hid, size=size, mode=mode, align_corners=False)
+        last = self.attn_mlp.layers[-1]
+        B, Q, c = qe.shape
+        n = self.total_heads
+        w3 = last.weight.view(n, c, -1)                                       # (n, c, k)
+        a = torch.matmul(qe[:, None], w3)                                     # (B, n, Q, k)
+        c0 = torch.matmul(qe, last.bias.view(n, c).t()).permute(0, 2, 1)      # (B, n, Q)
+        bias = torch.matmul(a, hid.flatten(2)[:, None]) + c0[..., None]       # (B, n, Q, P)
+        if isinstance(self.bias_scaling, nn.Linear):
+            bias = bias * self.bias_scaling.weight.view(()) + self.bias_scaling.bias.view(())
+        return bias.reshape(B, n, Q, *size)
+
+    def forward(self, query, x, bias_size=None, bias_mode=None):
+        """-> (mask_preds (B, Q, h, w), [attn_bias (B, heads, Q, h, w)] per bias layer).
+        ``bias_size`` / ``bias_mode``: the grid and the resize the recognition head would
+        apply to the bias; where ``bias_at_ok`` holds the bias then comes out AT that grid
+        (``attn_bias_at``), anything else leaves it at the decoder's own grid as before."""
         query = self.query_mlp(query)                 # (B, Q, c)
         pix = self.pix_mlp(x)                         # (B, c, h, w)
         b, c, h, w = pix.shape
         mask_preds = torch.einsum('bqc,bchw->bqhw', query, pix)
+        if bias_size is not None and self.bias_at_ok(bias_mode):
+            return mask_preds, [self.attn_bias_at(None, x, tuple(bias_size), bias_mode,
+                                                  query_embed=query)]
         attn = self.attn_mlp(x).reshape(b, self.total_layers, self.total_heads, c, h, w)
         if torch.is_grad_enabled():
             attn_bias = torch.einsum('bqc,blnchw->blnqhw', query, attn)
@@ -300,17 +351,20 @@ class RegionwiseSideAdapterNetwork(nn.Module):
                              rescale_attn_bias=rescale_attn_bias)
         return cls(vit, fusion, dec, num_queries, x2side, list(deep_supervision_idxs))
 
-    def forward(self, image, clip_features):
+    def forward(self, image, clip_features, bias_size=None, bias_mode=None):
+        """``bias_size`` / ``bias_mode``: handed to ``MLPMaskDecoder.forward`` (the
+        attention biases at the recognition head's grid where the decoder can)."""
         out_features, san_features = self.forward_features(image, clip_features)
-        mask_preds, attn_biases = self.decode_masks(out_features)
+        mask_preds, attn_biases = self.decode_masks(out_features, bias_size, bias_mode)
         return mask_preds, attn_biases, san_features
 
-    def decode_masks(self, features):
+    def decode_masks(self, features, bias_size=None, bias_mode=None):
         if not self.training:
             features = [features[-1]]
         mask_preds, attn_biases = [], []
         for feature in features:
-            m, a = self.mask_decoder(**feature)
+            at = {} if bias_size is None else dict(bias_size=bias_size, bias_mode=bias_mode)
+            m, a = self.mask_decoder(**feature, **at)
             mask_preds.append(m)
             attn_biases.append(a)
         return mask_preds, attn_biases
@@ -407,7 +461,7 @@ def semantic_inference_2d_w_embed(mask_cls, mask_embed, mask_pred):
 
 def semantic_branch_2d(side_net, rec_head, ov_classifier_weight, images, clip_feats,
                        native_tail=False, full=True, labels=False, group=None,
-                       n_merged=None):
+                       n_merged=None, hip_query=None):
     """The 2-D open-vocabulary branch of SANInVeonTemporal.forward
     (san_in_veon_temporal.py:123-139, 176-186) on one flattened camera batch
     ``images`` (B*N,3,H,W) and the CLIP feature dict of layers 0..K: mask proposals
@@ -420,9 +474,25 @@ def semantic_branch_2d(side_net, rec_head, ov_classifier_weight, images, clip_fe
     below.  Then ``full=False`` leaves ``sem_seg`` out (a training step reads only
     ``sem_seg_ds``) and ``labels=True`` adds ``labels_2d``, uint8 (B*N,H,W): the arg-max of
     ``sem_seg``, over the runs of rows of ``group`` / ``n_merged``
-    (``vocabulary.group_table``) when a detailed vocabulary is set."""
-    mask_preds, attn_biases, san_feats = side_net(images, clip_feats)
-    mask_embs = [rec_head(clip_feats, ab, normalize=True) for ab in attn_biases]
+    (``vocabulary.group_table``) when a detailed vocabulary is set.
+
+    ``hip_query`` (None: ``rec_head.hip_query``): the recognition head's native query path
+    (``ClipRecHead.hip_query``), and the attention bias asked from the mask decoder AT the
+    head's own (h, w) grid (``MLPMaskDecoder.attn_bias_at``) instead of being formed at the
+    side adapter's grid and resized by the head.  ``out['attn_biases']`` is then that
+    (B, heads, Q, h, w) tensor: the old one resized, up to the reassociation of fp32 sums;
+    where the decoder cannot (``bias_at_ok``) it stays at the decoder's grid as before."""
+    if hip_query is None:
+        hip_query = bool(getattr(rec_head, 'hip_query', False))
+    if hip_query:
+        grid = tuple(clip_feats[rec_head.first_layer_idx].shape[-2:])
+        mask_preds, attn_biases, san_feats = side_net(
+            images, clip_feats, bias_size=grid, bias_mode=rec_head.downsample_method)
+        mask_embs = [rec_head(clip_feats, ab, normalize=True, hip_query=True)
+                     for ab in attn_biases]
+    else:
+        mask_preds, attn_biases, san_feats = side_net(images, clip_feats)
+        mask_embs = [rec_head(clip_feats, ab, normalize=True) for ab in attn_biases]
     mask_logits = [torch.einsum('bqc,nc->bqn', e, ov_classifier_weight) for e in mask_embs]
     out = {'mask_preds': mask_preds[-1], 'attn_biases': attn_biases[-1],
            'mask_embs': mask_embs[-1], 'mask_logits': mask_logits[-1],

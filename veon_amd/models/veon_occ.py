@@ -53,6 +53,11 @@ class VeonOccupancyPath(nn.Module):
     # the semantic maps of the 2-D branch (``forward_2d``, ``forward(with_2d=True)``) from
     # the fused kernels of veon_amd/sem2d.py instead of the reference's torch lines
     hip_tail_2d = False
+    # the recognition head of the 2-D branch on the library: ``ClipRecHead``'s native query
+    # path and the attention bias taken at the CLIP grid (``semantic_branch_2d(hip_query=
+    # True)``); covers ``forward_2d``, ``forward(with_2d=True)`` and the training step's
+    # ``sem_seg_ds`` / ``sem_embed_ds``.  Independent of ``hip_tail_2d``.
+    hip_rec_head = False
 
     def __init__(self, input_size=(256, 704), grid_config=None, num_cam=6,
                  encoder='vitb', n_classes=17, clip_width=768, clip_layers=12,
@@ -224,14 +229,16 @@ class VeonOccupancyPath(nn.Module):
         from .semantic_net.side_adapter import semantic_branch_2d
         args = (self.side_adapter_network, self.clip_rec_head, self._classifier_weight(),
                 img, feats)
+        hq = True if self.hip_rec_head else None     # None: the head's own switch
         if not self.hip_tail_2d:
             if not full or labels:
                 raise ValueError('full=False and labels=True need hip_tail_2d = True')
-            return semantic_branch_2d(*args)
+            return semantic_branch_2d(*args, hip_query=hq)
         ov = self.__dict__['_ov']
         group = None if ov is None else ov['group'][:-1]   # without the background row
         return semantic_branch_2d(*args, native_tail=True, full=full, labels=labels,
-                                  group=group, n_merged=None if ov is None else ov['free_label'])
+                                  group=group, n_merged=None if ov is None else ov['free_label'],
+                                  hip_query=hq)
 
     def forward_2d(self, images, full=True, labels=False):
         """The 2-D open-vocabulary segmentation branch (san_in_veon_temporal.py:

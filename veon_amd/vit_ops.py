@@ -274,6 +274,83 @@ def attention(qkv, num_heads, bias=None, out=None, q_log2=False):
     return out
 
 
+# ------------------- query cross-attention with a self key (csrc/query_attention.hip)
+def _query_dims(q_qkv, mem_kv, num_heads):
+    """(B, Q, T, hd) of the operands of ``query_attention``: q_qkv [B, Q, 3*H*hd] or
+    [B, Q, 3, H, hd]; mem_kv [B, T, 2*H*hd] or [B, T, 2, H, hd]."""
+    H = num_heads
+    B, Q = q_qkv.shape[:2]
+    hd = q_qkv[0, 0].numel() // (3 * H)
+    T = mem_kv.shape[1]
+    assert q_qkv.dim() in (3, 5) and q_qkv[0, 0].numel() == 3 * H * hd
+    assert mem_kv.dim() in (3, 5) and mem_kv.shape[0] == B
+    assert mem_kv[0, 0].numel() == 2 * H * hd
+    return B, Q, T, hd
+
+
+def query_attention(q_qkv, mem_kv, num_heads, bias=None, key0=0, q_log2=False, out=None):
+    """The attention core of ``cross_attn_with_self_bias`` (models/semantic_net/
+    clip_blocks.py) as one launch of ``veon_query_attention``
+    (include/ext/veon_hip_query.h): q_qkv half [B, Q, 3, H, 64], the packed projection of
+    the query tokens (q pre-scaled by 64^-0.5; ``q_log2``: also by ``LOG2E``); mem_kv half
+    [B, T, 2, H, 64], the k / v projection of the memory tokens -- it may be a VIEW with any
+    token stride (the K/V part ``qkv.view(B, T, 3, H, 64)[:, :, 1:]`` of a packed buffer);
+    the keys are tokens ``key0 .. T-1``.  bias: optional fp32 additive logits
+    (B | 1, H | 1, Q, T - key0), natural-log units, -inf removes a key.  Every query also
+    attends to itself through its own k / v rows.  -> half [B, Q, H*64]."""
+    dev = _dev(q_qkv, mem_kv, bias, out)
+    _lib.require_half(q_qkv, mem_kv, out)
+    H = num_heads
+    B, Q, T, hd = _query_dims(q_qkv, mem_kv, H)
+    if hd != 64:
+        raise _lib.VeonHipError('query_attention: head_dim %d, the kernel takes 64' % hd)
+    assert q_qkv.is_contiguous()
+    tok = mem_kv.stride(1) if T > 1 else 2 * H * hd
+    inner = (H * hd, hd, 1) if mem_kv.dim() == 5 else (1,)
+    assert tuple(mem_kv.stride()[2:]) == inner, 'mem_kv: the rows of a token must be dense'
+    assert B == 1 or mem_kv.stride(0) == T * tok, 'mem_kv: images must follow each other'
+    Lk = T - key0
+    sb = sh = 0
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.dim() == 4
+        assert bias.shape[0] in (1, B) and bias.shape[1] in (1, H)
+        assert bias.shape[-2:] == (Q, Lk)
+        if Lk and (bias.stride(-1) != 1 or (Q > 1 and bias.stride(-2) != Lk)):
+            bias = bias.contiguous()
+        sb = bias.stride(0) if bias.shape[0] > 1 else 0
+        sh = bias.stride(1) if bias.shape[1] > 1 else 0
+    if out is None:
+        out = torch.empty((B, Q, H * hd), dtype=_half.dtype(), device=dev)
+    assert out.is_contiguous() and out.shape == (B, Q, H * hd)
+    _lib.launch('veon_query_attention', dev, q_qkv, mem_kv, int(tok), bias, int(sb), int(sh),
+                out, B, Q, T, int(key0), H, int(bool(q_log2)))
+    return out
+
+
+def query_attention_ref(q_qkv, mem_kv, num_heads, bias=None, key0=0, q_log2=False,
+                        dtype=torch.float64):
+    """``query_attention`` in torch on the operands as given, q k v in ``dtype`` (fp64 for
+    a reference; any head_dim): logits s_j = q.k_j + bias_j over the memory keys
+    ``key0 .. T-1`` and s_self = q.k_q, one softmax over the Lk + 1 of them,
+    out = sum_j p_j v_j + p_self v_q.  The scores are promoted to the bias's precision
+    before it is added; ``q_log2``: q carries log2(e), which is taken out of the scores."""
+    H = num_heads
+    B, Q, T, hd = _query_dims(q_qkv, mem_kv, H)
+    x = q_qkv.reshape(B, Q, 3, H, hd).to(dtype)
+    mem = mem_kv.reshape(B, T, 2, H, hd)[:, key0:].to(dtype)
+    q, kq, vq = x.permute(2, 0, 3, 1, 4)               # (B, H, Q, hd)
+    k, v = mem.permute(2, 0, 3, 1, 4)                  # (B, H, Lk, hd)
+    s = torch.cat([q @ k.transpose(-2, -1), (q * kq).sum(-1, keepdim=True)], dim=-1)
+    if q_log2:
+        s = s / LOG2E
+    if bias is not None:
+        s = s.to(torch.promote_types(s.dtype, bias.dtype))
+        s = torch.cat([s[..., :-1] + bias, s[..., -1:]], dim=-1)
+    p = s.softmax(dim=-1).to(dtype)
+    o = p[..., :-1] @ v + p[..., -1:] * vq
+    return o.transpose(1, 2).reshape(B, Q, H * hd)
+
+
 # ------------------------------------------- attention for training (csrc/attention_train.hip)
 def attention_stats_len(T):
     """Floats per (b, h) row of ``lse`` and of the backward's workspace: T rounded up to 64."""
